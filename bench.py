@@ -9,14 +9,20 @@ analysis (STFT -> IBM -> masked covariance partials), solve (fp64 MVDR), synthes
 normalisation) kernels, inputs resident in HBM. The timed steps alternate between two
 distinct batches (2 x 262 MB of input, more than the 256 MB Infinity Cache), so no step
 re-reads the previous step's input from the die. Per-kernel times come from HIP events the
-plan records around each launch on the launch stream (avz_plan_set_timing).
+plan records around each launch on the launch stream (avz_plan_set_timing), with --full.
 Multi-GPU: one process per GPU, utterances sharded (weak scaling, no data-path
 collective); the only collectives are the final RCCL all-reduce of the SIR metric sums
 and the max-over-ranks step time. With --gpus N > 1 the per-GPU shard defaults to
 configs[2]'s (B = 4096 over 8 GPUs = 512 utterances per GPU, 3 interferers).
 
-The N = 1 default run also measures, in the same JSON line (`secondary`), every other
-single-GPU configuration the same way: configs[2]'s per-GPU shard, configs[3] (IPD,
+A plain run sets up, settles the clock, warms up, times the K steps, writes the last timed
+step's outputs (--dump-outputs DIR) and prints the result line. Everything else is behind
+--full: the CPU baseline, the per-kernel HIP events and their roofline entries, the
+PCIe-inclusive rate, the SIR metrics and their comparison with the oracle, the U-Net
+workload's parts timed alone, and the secondary configurations.
+
+The N = 1 default run with --full also measures, in the same JSON line (`secondary`), every
+other single-GPU configuration the same way: configs[2]'s per-GPU shard, configs[3] (IPD,
 B = 1024), oracle_debug's 512/256 STFT, the batch driver's deferred normalisation and
 configs[4]'s MVDR chain (4096 two-second external-mask items).
 
@@ -31,6 +37,7 @@ Other workloads (parity configs, measured on request, same JSON line):
                    MVDR chain are also timed alone
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload W]
+                       [--dump-outputs DIR] [--full]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 """
 from __future__ import annotations
@@ -78,6 +85,15 @@ def parse():
                     help="utterances per GPU (0: workload default; ibm at N > 1: 512, configs[2])")
     ap.add_argument("--interferers", type=int, default=0,
                     help="interferers per scene (0: 2; ibm at N > 1: 3, configs[2])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: CPU "
+                         "baseline, per-kernel events and roofline, PCIe-inclusive rate, SIR "
+                         "metrics vs the oracle, the secondary configurations (the --no-* and "
+                         "--secondary options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed (out, peak) as DIR/<name>.npy, "
+                         "float32; an array over 48 MiB is cut to a fixed seeded sample of the "
+                         "batch's rows")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
                     help="time box of the CPU baseline workers")
     ap.add_argument("--cpu-workers", type=int, default=0,
@@ -207,6 +223,8 @@ UNET_SECONDARY_STEPS = 2  # configs[4] end to end in the default run: ~1.4 s per
 SETTLE_BLOCK = 20  # steps per clock-settling block
 SETTLE_MIN_S = 0.1  # sustained load before the convergence test (the clock ramps for tens of ms)
 SETTLE_MAX_S = 0.6  # cap on the settling phase
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: budget of the sampled [rows, samples] output
+DUMP_SEED = 20250101  # --dump-outputs: seed of the row sample
 
 
 def bytes_per_bin(workload, n_fft):
@@ -262,6 +280,11 @@ def setup_chain(spec, dev, batches):
         plan.run(s["mix"], lens, max_len=S, out=s["out"], peak=s["peak"], **s["refs"])
 
     n_out = plan.out_len(S)
+
+    def outputs():  # what the caller of the last step received (out without its row padding)
+        s = sets[(it[0] - 1) % len(sets)]
+        return {"out": s["out"][:, :n_out], "peak": s["peak"]}
+
     F, T = n_fft // 2 + 1, -(-S // hop) + 1
     nch = -(-T // 32)
     s0 = sets[0]
@@ -280,7 +303,7 @@ def setup_chain(spec, dev, batches):
                 design_kernel={"synthesis": design_syn, "finalize": 2 * alg_syn},
                 kernel_names={"synthesis": syn_name, "solve": f"avz_solve_kernel<{n_fft}>",
                               "finalize": f"avz_finalize_kernel<{n_fft}>"},
-                mix=s0["mix"], refs=s0["refs"], sets=sets, it=it)
+                mix=s0["mix"], refs=s0["refs"], sets=sets, it=it, outputs=outputs)
     return step, info
 
 
@@ -300,7 +323,7 @@ def setup_unet(spec, dev, batches, unet_dtype):
     def step():
         d_mix = batches[it[0] % len(batches)][0]
         it[0] += 1
-        y["out"], _ = bf.run(d_mix)
+        y["out"], y["peak"] = bf.run(d_mix)
 
     n_fft = spec["n_fft"]
     F = n_fft // 2 + 1
@@ -309,7 +332,8 @@ def setup_unet(spec, dev, batches, unet_dtype):
     info = dict(plan=bf.plan, bf=bf, bins=n_items * F * Tc, n_items=n_items,
                 alg_analysis=n_items * 2 * bf.chunk * 4,
                 alg_chain=n_items * (2 * bf.chunk * 4 + n_out * 4),
-                kernel=f"avz_analysis_kernel<{n_fft},EXTERNAL>", mix=batches[0][0], y=y, it=it)
+                kernel=f"avz_analysis_kernel<{n_fft},EXTERNAL>", mix=batches[0][0], y=y, it=it,
+                outputs=lambda: dict(y))
     return step, info
 
 
@@ -565,9 +589,32 @@ def configs0_latency(dev, n_calls=50):
     return res
 
 
-def run_timed(step, plan, K, W, world, dev, settle_on, kernel_timing):
+def dump_outputs(outputs, outdir, rank):
+    """--dump-outputs: the arrays of `outputs` as outdir/<name>.npy (float32; ranks > 0 add
+    _rank<r> to the name). A 2-D array over DUMP_MAX_BYTES is cut to a fixed sample of its
+    rows (DUMP_SEED, sorted), the same rows on every run of the same arguments."""
+    os.makedirs(outdir, exist_ok=True)
+    written = {}
+    for name, t in outputs.items():
+        rows = None
+        row_bytes = 4 * t[0].numel() if t.dim() > 1 else 0
+        if row_bytes and t.shape[0] * row_bytes > DUMP_MAX_BYTES:
+            n = max(1, DUMP_MAX_BYTES // row_bytes)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], n, replace=False))
+            t = t[rows.tolist()]
+        a = np.ascontiguousarray(t.float().cpu().numpy())
+        np.save(os.path.join(outdir, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype),
+                         "rows": None if rows is None else f"{len(rows)} sampled (seed {DUMP_SEED})"}
+    return written
+
+
+def run_timed(step, plan, K, W, world, dev, settle_on, kernel_timing, it=None, after_timed=None):
     """Clock settling, W warmup steps, K timed steps (barrier + synchronize on both sides),
-    then an untimed pass with HIP events around all four kernels."""
+    then (kernel_timing) an untimed pass with HIP events around all four kernels. `it`: the
+    step counter, restarted after the settling blocks (whose number varies) so that the warmup
+    and timed steps visit the input batches in the same order on every run; after_timed() runs
+    right after the timed steps, before any further step overwrites their outputs."""
     import torch
     import torch.distributed as dist
     # Clock settling: a GPU that sat idle (host scene setup, the CPU baseline) runs its
@@ -598,6 +645,8 @@ def run_timed(step, plan, K, W, world, dev, settle_on, kernel_timing):
             if done or time.perf_counter() - s0 > SETTLE_MAX_S:
                 break
         settle["ms"] = 1e3 * (time.perf_counter() - s0)
+    if it is not None:
+        it[0] = 0
     for _ in range(W):
         step()
     torch.cuda.synchronize()
@@ -620,6 +669,8 @@ def run_timed(step, plan, K, W, world, dev, settle_on, kernel_timing):
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
+    if after_timed is not None:
+        after_timed()
     kt = None
     if kernel_timing:
         dom = plan.timing()  # the bracketed steps among the K timed ones
@@ -694,8 +745,10 @@ def main():
     from avz import synth
     gen_host = synth.make_batch_philox if args.scenes == "philox" else synth.make_batch
 
+    full = args.full
+    kernel_timing = full and not args.no_kernel_timing
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and args.workload != "unet":
+    if full and rank == 0 and world == 1 and not args.no_cpu and args.workload != "unet":
         available, quota = cpu_share()
         share = min(CPU_SHARE, available)
         if quota is not None:
@@ -742,19 +795,25 @@ def main():
         step, info = setup_chain(spec, dev, batches)
     plan = info["plan"]
     K = args.steps
+    dumped = {}
+
+    def after_timed():  # the last timed step's outputs, before any later step rewrites them
+        if args.dump_outputs:
+            dumped.update(dump_outputs(info["outputs"](), args.dump_outputs, rank))
+
     # a U-Net step alone takes ~1.4 s: no settling blocks for it
     elapsed_s, kt, settle = run_timed(step, plan, K, args.warmup, world, dev,
                                       not args.no_settle and args.workload != "unet",
-                                      not args.no_kernel_timing)
+                                      kernel_timing, it=info["it"], after_timed=after_timed)
     elapsed = torch.tensor([elapsed_s], dtype=torch.float64, device=dev)
     step_ms = 1e3 * elapsed_s / K
     chain_ms = sum(kt[k] for k in plan.KERNELS) if kt else step_ms
 
     extra = {}
-    if args.workload == "unet":  # the U-Net forward alone (features included), same items
+    if full and args.workload == "unet":  # the U-Net forward alone (features included), same items
         extra.update(unet_figures(info, K, chain_ms))
 
-    if args.workload != "unet" and rank == 0:
+    if full and args.workload != "unet" and rank == 0:
         try:
             # PCIe-inclusive rate (not `value`): the same step with its inputs copied from
             # pinned host memory first and the output copied back (host-buffer callers, e.g.
@@ -784,41 +843,46 @@ def main():
         except Exception as exc:  # a side figure must never sink the bench line
             extra["pcie_inclusive"] = {"error": repr(exc)[:200]}
 
-    # ---- final metrics: projection SIR per utterance (run_metrics.py:6-36), RCCL all-reduce
-    # of batch 0's outputs: one more step on batch 0 leaves them in its output buffer
-    info["it"][0] = 0
-    step()
-    torch.cuda.synchronize()
+    # ---- final metrics (--full): projection SIR per utterance (run_metrics.py:6-36), RCCL
+    # all-reduce, of batch 0's outputs: one more step on batch 0 leaves them in its output buffer
+    sums = sir_out = None
     L = S
-    if args.workload == "unet":
-        est_out = info["y"]["out"][:, :L]
-    else:
-        est_out = info["out"][:, :L]
-        L = est_out.shape[1]
-    d_tgt, d_itf = d_tgt[:, :L], d_itf[:, :L]
-    est = torch.cat([est_out, d_mix[:, 0, :L]])
-    est_peak = None
-    if args.workload != "unet" and args.normalize == "deferred":  # score out / peak
-        eps = 1e-6 if args.workload == "ipd" else 0.0
-        est_peak = torch.cat([info["peak"] + eps, torch.ones_like(info["peak"])])
-    m = metrics.projection_metrics(est, torch.cat([d_tgt] * 2), torch.cat([d_itf] * 2),
-                                   est_peak=est_peak)
-    sir_out, sir_in = m[:B, 3], m[B:, 3]
-    # [sum SIR_in, sum SIR_out, sum OSINR_out, n_ok, n] over the utterances
-    # whose metrics are finite (batch_run.finite_sums)
-    sums = finite_sums([sir_in, sir_out, m[:B, 0]], B)
-    if world > 1:  # SUM of the metric sums, MAX over ranks of the timings
+    if full:
+        info["it"][0] = 0
+        step()
+        torch.cuda.synchronize()
+        if args.workload == "unet":
+            est_out = info["y"]["out"][:, :L]
+        else:
+            est_out = info["out"][:, :L]
+            L = est_out.shape[1]
+        d_tgt, d_itf = d_tgt[:, :L], d_itf[:, :L]
+        est = torch.cat([est_out, d_mix[:, 0, :L]])
+        est_peak = None
+        if args.workload != "unet" and args.normalize == "deferred":  # score out / peak
+            eps = 1e-6 if args.workload == "ipd" else 0.0
+            est_peak = torch.cat([info["peak"] + eps, torch.ones_like(info["peak"])])
+        m = metrics.projection_metrics(est, torch.cat([d_tgt] * 2), torch.cat([d_itf] * 2),
+                                       est_peak=est_peak)
+        sir_out, sir_in = m[:B, 3], m[B:, 3]
+        # [sum SIR_in, sum SIR_out, sum OSINR_out, n_ok, n] over the utterances
+        # whose metrics are finite (batch_run.finite_sums)
+        sums = finite_sums([sir_in, sir_out, m[:B, 0]], B)
+    if world > 1:  # SUM of the metric sums (--full), MAX over ranks of the timings
         kn = plan.KERNELS + ("analysis_timed",)
         mx = torch.tensor([elapsed_s, step_ms, chain_ms] + ([kt[k] for k in kn] if kt else []),
                           dtype=torch.float64, device=dev)
-        allreduce_job(sums, mx)
+        if sums is not None:
+            allreduce_job(sums, mx)
+        else:
+            dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         elapsed = mx[:1]
         step_ms, chain_ms = float(mx[1]), float(mx[2])
         if kt:
             kt.update({k: float(mx[3 + j]) for j, k in enumerate(kn)})
     # SIR delta vs the reference restatement on identical inputs (rank 0, few utterances)
     d_sir = None
-    if rank == 0 and args.workload != "unet":
+    if full and rank == 0 and args.workload != "unet":
         k = min(B, 4)
         got = sir_out[:k].cpu().numpy()
         mix, tgt, itf = (x[:k].cpu().numpy() for x in (d_mix, d_tgt, d_itf))
@@ -897,7 +961,7 @@ def main():
     secondary = None
     default_run = (args.workload == "ibm" and N_FFT == 1024 and B == 256 and args.interferers == 2
                    and args.normalize == "peak")
-    if world == 1 and default_run and not args.no_secondary:
+    if full and world == 1 and default_run and not args.no_secondary:
         del batches, d_mix, d_tgt, d_itf, est, m, info, step
         torch.cuda.empty_cache()
         secondary = {}
@@ -1016,12 +1080,16 @@ def main():
             "config": cfg,
             "roofline": roof,
             "cpu_baseline": cpu,
-            "sir": {"sir_in_mean_db": float(sums[0] / max(float(sums[3]), 1.0)),
-                    "sir_out_mean_db": float(sums[1] / max(float(sums[3]), 1.0)),
-                    "osinr_out_mean_db": float(sums[2] / max(float(sums[3]), 1.0)),
-                    "sir_abs_delta_vs_reference_db": d_sir, "n_ok": int(sums[3]),
-                    "n_utts": int(sums[4])},
+            "full": full,
         }
+        if sums is not None:
+            line["sir"] = {"sir_in_mean_db": float(sums[0] / max(float(sums[3]), 1.0)),
+                           "sir_out_mean_db": float(sums[1] / max(float(sums[3]), 1.0)),
+                           "osinr_out_mean_db": float(sums[2] / max(float(sums[3]), 1.0)),
+                           "sir_abs_delta_vs_reference_db": d_sir, "n_ok": int(sums[3]),
+                           "n_utts": int(sums[4])}
+        if args.dump_outputs:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         line.update(extra)
         if secondary is not None:
             line["secondary"] = secondary

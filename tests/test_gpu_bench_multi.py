@@ -33,7 +33,7 @@ def _rank(rank, world, port, out_path):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     sys.path.insert(0, ROOT)
-    sys.argv = ["bench.py", "--gpus", str(world), "--rehearse-shared-gpu", "--no-cpu",
+    sys.argv = ["bench.py", "--gpus", str(world), "--full", "--rehearse-shared-gpu", "--no-cpu",
                 "--steps", str(STEPS), "--warmup", "1", "--no-settle"]
     import bench
     with open(out_path + f".{rank}", "w") as f:
@@ -69,7 +69,7 @@ def test_bench_two_ranks_shared_gpu(tmp_path, gpu_device):
     assert line["sir"]["n_utts"] == 1024 and line["sir"]["n_ok"] == 1024
 
     # one process over the same 1024 utterances (batch 0 = utterances 0 .. 1023)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "1024",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--batch", "1024",
                         "--interferers", "3", "--no-cpu", "--no-secondary", "--steps", "2",
                         "--warmup", "1", "--no-settle", "--no-kernel-timing"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT,

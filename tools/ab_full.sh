@@ -9,7 +9,7 @@ timeout -k 10 420 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 $out/gpu_tests.log
 for rep in $(seq 1 ${REPS:-2}); do
 for lib in "$@"; do
-  AVZ_LIB=$D/$lib timeout -k 10 300 python bench.py --no-cpu > $out/bench_${lib}_$rep.log 2>&1 || { tail -20 $out/bench_${lib}_$rep.log; exit 1; }
+  AVZ_LIB=$D/$lib timeout -k 10 300 python bench.py --full --no-cpu > $out/bench_${lib}_$rep.log 2>&1 || { tail -20 $out/bench_${lib}_$rep.log; exit 1; }
   tail -1 $out/bench_${lib}_$rep.log | python3 -c '
 import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]
 print(sys.argv[1], round(d["value"]/1e9,2), "G", {k: round(v*1e3,1) for k,v in r["kernels_ms"].items()}, "dom", round(r["dominant_kernel"]["kernel_ms"]*1e3,1))

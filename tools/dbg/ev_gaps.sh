@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 out=gpurun_out/${1:-ev2}
 mkdir -p $out
 for i in 1 2; do
-  timeout -k 10 100 python bench.py --no-cpu > $out/t_$i.log 2>&1 || exit 1
-  timeout -k 10 100 python bench.py --no-cpu --no-kernel-timing > $out/n_$i.log 2>&1 || exit 1
+  timeout -k 10 100 python bench.py --full --no-cpu > $out/t_$i.log 2>&1 || exit 1
+  timeout -k 10 100 python bench.py --full --no-cpu --no-kernel-timing > $out/n_$i.log 2>&1 || exit 1
 done
 timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $out/prof -o run -- python3 bench.py --no-cpu --steps 10 --no-kernel-timing > $out/prof.log 2>&1 || exit 1
 for f in $out/t_*.log $out/n_*.log; do

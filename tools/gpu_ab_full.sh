@@ -7,7 +7,7 @@ TAG=$1; shift
 D=real-time-audio-visual-zooming_amd/avz
 mkdir -p gpurun_out/$TAG
 for lib in "$@"; do
-  AVZ_LIB=$D/$lib timeout -k 10 400 python -u bench.py --no-cpu ${BENCH_ARGS} \
+  AVZ_LIB=$D/$lib timeout -k 10 400 python -u bench.py --full --no-cpu ${BENCH_ARGS} \
     > gpurun_out/$TAG/bench_${lib}.log 2>&1 || { tail -20 gpurun_out/$TAG/bench_${lib}.log; exit 1; }
   tail -1 gpurun_out/$TAG/bench_${lib}.log | python3 -c '
 import json,sys

@@ -7,7 +7,7 @@ out=gpurun_out/$tag
 mkdir -p $out
 for rep in $(seq 1 ${REPS:-1}); do
 for v in "$@"; do
-  AVZ_SYNTH_VARIANT=$v timeout -k 10 400 python bench.py --no-cpu ${BENCH_ARGS} > $out/bench_v${v}_$rep.json 2> $out/bench_v${v}_$rep.err || { tail -5 $out/bench_v${v}_$rep.err; exit 1; }
+  AVZ_SYNTH_VARIANT=$v timeout -k 10 400 python bench.py --full --no-cpu ${BENCH_ARGS} > $out/bench_v${v}_$rep.json 2> $out/bench_v${v}_$rep.err || { tail -5 $out/bench_v${v}_$rep.err; exit 1; }
   python3 - $out/bench_v${v}_$rep.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 set -o pipefail
 out=gpurun_out/${1:-bc}; mkdir -p $out
-t0=$(date +%s); timeout -k 10 400 python bench.py > $out/bench.log 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+t0=$(date +%s); timeout -k 10 400 python bench.py --full > $out/bench.log 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 echo "bench wall $(( $(date +%s) - t0 )) s"
 python3 - $out/bench.log <<'PY'
 import json, sys

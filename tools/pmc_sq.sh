@@ -14,7 +14,7 @@ i=0
 for P in "$P1" "$P2" "$P3"; do
   i=$((i+1))
   timeout -k 10 120 rocprofv3 --pmc $P --output-format csv -d $out/p$i -o run \
-    -- python3 bench.py --no-cpu --steps 5 --warmup 2 --no-kernel-timing "$@" > $out/p$i.log 2>&1 || { tail -20 $out/p$i.log; exit 1; }
+    -- python3 bench.py --full --no-cpu --steps 5 --warmup 2 --no-kernel-timing "$@" > $out/p$i.log 2>&1 || { tail -20 $out/p$i.log; exit 1; }
 done
 python3 - $out <<'PY' | tee $out/sq_counters.txt
 import csv, glob, sys, collections
