@@ -103,6 +103,9 @@ typedef struct avz_config {
                         clear an error bound of ibm_kappa * 2^-24 * ||windowed frame||, or
                         the frame's decision is recomputed from fp64 reference spectra
                         rounded to complex64 with numpy's |.|.
+                        A frame whose reference energy is outside the range in which fp32
+                        neither underflows nor overflows in that test (2^-56 .. 2^100 for
+                        N = 1024 at kappa 16) is recomputed whole unless it is all zeros.
                         0 = AVZ_IBM_KAPPA; < 0 = no certificate (fp32 decisions only). */
 } avz_config;
 /* 16: the bound 3.9 kappa eps ||z|| max|Z| covers the largest fp32-transform error seen in

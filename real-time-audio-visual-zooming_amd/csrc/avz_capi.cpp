@@ -113,6 +113,7 @@ struct avz_plan {
   double* xtw;               // [N][2] W_N^j, fp64 (exact IBM path)
   float* xwin;               // [N] the reference's fp32 Hann window (exact IBM path)
   float ibm_cert;            // ibm_kappa * 2^-24 (0: no certificate)
+  uint32_t ibm_en_lo, ibm_en_span;  // the certificate's level rule (avz::ibm_level_range)
   unsigned long long* xstat; // avz_plan_set_ibm_stats (diagnostic) or null
   int synth_variant;         // avz_plan_set_diagnostics (default 2)
   int dbg_ipf;               // avz_plan_set_diagnostics (default 0)
@@ -266,6 +267,11 @@ extern "C" int avz_plan_create(avz_plan** out, const avz_config* cfg) {
     }
     const double kappa = c.ibm_kappa == 0.0 ? AVZ_IBM_KAPPA : c.ibm_kappa;
     p->ibm_cert = kappa > 0.0 ? (float)(kappa * 0x1p-24) : 0.0f;
+    // delta per unit sqrt(energy): the reference-bit path (N = 1024 without the IRM gains) sums
+    // the raw samples, the per-bin paths the windowed ones
+    const bool refbits = c.n_fft == 1024 && c.postfilter != AVZ_PF_IRM;
+    avz::ibm_level_range(refbits ? (double)p->ibm_cert * 2.0 / c.n_fft : (double)p->ibm_cert,
+                         &p->ibm_en_lo, &p->ibm_en_span);
     p->xstat = nullptr;
     p->synth_variant = 2;
     p->dbg_ipf = 0;
@@ -364,6 +370,8 @@ static void plan_params(const avz_plan* p, avz::ChainArgs& k) {
   k.cond_max = c.cond_max;
   k.steer = p->steer;
   k.ibm_cert = p->ibm_cert;
+  k.ibm_en_lo = p->ibm_en_lo;
+  k.ibm_en_span = p->ibm_en_span;
   k.xwin = p->xwin;
   k.xtw = p->xtw;
   k.xstat = p->xstat;

@@ -225,11 +225,24 @@ __device__ __forceinline__ void window_fft_reg(cf (&v)[32], const WinCoef<1024>&
 // publishes no noise bits and returns true: the item's exact path decides it
 // (ibm_exact_item). delta goes to dl; the Nyquist bin (lane 0, k = 16, left in spec[N / 2])
 // is certified by the bin phase's Nyquist wave with it.
-// true when the pair's decision is not certified by the error bound dl (= delta)
+//
+// Level rule (ibm_level_range, avz_internal.h): the test above is trusted only on fp32 values
+// that neither underflowed nor overflowed, which the frame's energy settles. A frame whose
+// energy is outside [ibm_en_lo, ibm_en_lo + ibm_en_span] (one unsigned compare on its bits; 0,
+// inf and NaN are outside) is deferred whole -- every bin uncertain, the Nyquist bin by a
+// delta of inf (reference-bit path) or NaN -- unless every reference sample of it is exactly
+// 0 (zero padding, the generator's silent blocks: the reference's 0 > 0 is false, as the fp32
+// decision).
+// true when the pair's decision is not certified by the error bound dl (= delta); the negated
+// compare makes a NaN bound (a frame the level rule defers) or a NaN product uncertain
 __device__ __forceinline__ bool ibm_uncertain(cf zr, cf zrp, float dl) {
   const float d = fmaf(zr.x, zrp.x, -(zr.y * zrp.y));
   const float m = fmaxf(fmaxf(fabsf(zr.x), fabsf(zr.y)), fmaxf(fmaxf(fabsf(zrp.x), fabsf(zrp.y)), dl));
-  return fabsf(d) < 3.9f * dl * m;
+  return !(fabsf(d) >= 3.9f * dl * m);
+}
+// the level rule's compare: the energy's bits outside [lo, lo + span] (negative: never)
+__device__ __forceinline__ bool ibm_level_out(float en, uint32_t lo, uint32_t span) {
+  return __float_as_uint(en) - lo > span;
 }
 template <class After = NoAfter>
 __device__ __forceinline__ uint32_t window_fft_reg_ibm_bits(cf (&v)[32], const WinCoef<1024>& wc,
@@ -749,10 +762,11 @@ __device__ __forceinline__ void analysis_item(const ChainArgs& A, unsigned char*
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
   const int L = utt_len(A, b);
-  if (L < N) return;  // host validates; finalize reports NaN for a bad device length
   const int T = (L + H - 1) / H + 1;
   const int nch = (T + kChunk - 1) / kChunk;
-  if (c >= nch) return;
+  // L < N: host validates; finalize reports NaN for a bad device length. A skipped unit writes
+  // no exact-path record (ibm_exact_units skips it the same way).
+  if (L < N || c >= nch) return;
   if (c == 0 && p == 0 && tid == 0) {
     A.peak_u[b] = 0u;
     if (A.peak && A.normalize != NORM_PEAK) A.peak[b] = 0.0f;  // finalize's atomicMax target
@@ -896,8 +910,31 @@ __device__ __forceinline__ void analysis_item(const ChainArgs& A, unsigned char*
       if constexpr (REFBITS && !AVZ_NO_IBM_CERT && (AVZ_CERT_PARTS & 1)) {
         if (ref) {
           const float eg = group32_sum(frame_energy(v));
-          eg0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(eg), 0));
-          eg1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(eg), 32));
+          // (kept as bits: the level rule's compare and selects stay scalar)
+          int e0 = __builtin_amdgcn_readlane(__float_as_int(eg), 0);
+          int e1 = __builtin_amdgcn_readlane(__float_as_int(eg), 32);
+          const bool o0 = (uint32_t)e0 - A.ibm_en_lo > A.ibm_en_span;  // ibm_level_out
+          const bool o1 = (uint32_t)e1 - A.ibm_en_lo > A.ibm_en_span;
+          if ((o0 || o1) && A.ibm_cert > 0.0f) {  // rare (wave-uniform): all-zero frames pass
+            uint32_t nz = 0u;
+            static_for<0, 32>([&](auto r) { nz |= __float_as_uint(v[r].x) | __float_as_uint(v[r].y); });
+            const unsigned long long any = __ballot((nz << 1) != 0u);  // -0 is zero
+            const bool f0 = o0 && (uint32_t)any != 0u, f1 = o1 && (any >> 32) != 0ull;
+            if (f0 || f1) {
+              // deferred whole, through the certificate itself: a zero frame under delta = inf
+              // fails the test in every bin, the Nyquist bin included, whatever its samples
+              // would have overflowed or underflowed to (the exact path reads them from memory)
+              const bool mine = lm.grp ? f1 : f0;
+              static_for<0, 32>([&](auto r) {
+                v[r].x = mine ? 0.0f : v[r].x;
+                v[r].y = mine ? 0.0f : v[r].y;
+              });
+              e0 = f0 ? 0x7f800000 : e0;  // inf
+              e1 = f1 ? 0x7f800000 : e1;
+            }
+          }
+          eg0 = __int_as_float(e0);
+          eg1 = __int_as_float(e1);
         }
       }
       if constexpr (MASK == MASK_IPD) {
@@ -957,6 +994,27 @@ __device__ __forceinline__ void analysis_item(const ChainArgs& A, unsigned char*
         }
       } else {
         window_fft_reg(v, wc, fft, my_spec, tw_reg, lm, load_reg, (DLT && ref) ? &en : nullptr);
+      }
+      if constexpr (DLT) {
+        static_assert(C::FPW == 2, "lane groups of 32");
+        if (ref) {  // the level rule on the windowed energy
+          const bool o = ibm_level_out(en, A.ibm_en_lo, A.ibm_en_span);
+          if (__ballot(o) != 0ull && A.ibm_cert > 0.0f) {  // rare (wave-uniform)
+            // the frame's samples once more (v holds its spectrum, or the next step's loads):
+            // an all-zero frame passes
+            const int sf = (t0 + step * FB + my_frame) * H - N / 2 + (lane & 31);
+            uint32_t nz = 0u;
+#pragma unroll 1
+            for (int r = 0; r < N / 32; r += 4) {
+#pragma unroll
+              for (int q = 0; q < 4; ++q)
+                nz |= __float_as_uint(bload(r_re, sf + 32 * (r + q))) |
+                      __float_as_uint(bload(r_im, sf + 32 * (r + q)));
+            }
+            const unsigned long long any = __ballot((nz << 1) != 0u);  // -0 is zero
+            if (o && ((any >> (32 * lm.grp)) & 0xffffffffull) != 0ull) en = __builtin_nanf("");
+          }
+        }
       }
       // IBM: the reference waves publish each frame's certificate scale delta (the bin phase's
       // per-bin deferrals, the Nyquist bin's); the reference-bit path returns delta itself
@@ -1820,6 +1878,14 @@ __device__ __forceinline__ void ibm_exact_units(unsigned char* lds, int gx, int 
     if (!((mine >> min(k, 31)) & 1u)) return;
     const uint4 rec = reinterpret_cast<const uint4*>(A.xpend)[u];  // block-uniform
     if (rec.x == 0u || rec.w != 0u) return;
+    if (k >= 31) {
+      // bit 31 stands for every unit past the 31st: one of them that analysis_item skipped
+      // (its chunk is past the utterance's end) wrote no record, and an earlier call's sits here
+      int b, c;
+      unit_item<G::F>(A, u, gx, n_items, n_whole, P, b, c);
+      const int L = utt_len(A, b);
+      if (L < N || c >= ((L + G::H - 1) / G::H + 1 + kChunk - 1) / kChunk) return;
+    }
     if (!have_tables) {
       tables();
       have_tables = true;

@@ -1,6 +1,7 @@
 // avz_internal.h — host/device shared argument blocks (not part of the public ABI).
 #pragma once
 #include <stdint.h>
+#include <string.h>
 
 namespace avz {
 
@@ -19,6 +20,53 @@ static_assert(sizeof(PieceState) == 16, "one 16-B store resets it");
 
 // Pieces a shared unit of the exact IBM path splits into at most (avz_chunked_k.hpp XPieces).
 constexpr int kXPieces = 8;
+
+// Level rule of the exact-IBM certificate (avz_chunked_k.hpp ibm_uncertain): the frame
+// energies E for which an fp32 decision may be certified at all, as float bits [lo, lo + span]
+// (positive floats order as their bits, so the kernels test `bits(E) - lo > span`, unsigned:
+// one compare that also sends 0, inf and NaN outside). c is delta per unit sqrt(E): delta =
+// c sqrt(E), with E the energy the kernel sums -- raw samples and c = cert 2 / N on the
+// reference-bit path (2 / N: the scaled window's maximum), windowed samples and c = cert on
+// the per-bin paths. Either way every windowed sample, transform intermediate and spectrum
+// component of the frame is at most sqrt(2 N) sqrt(E) <= 2^6 sqrt(E) in magnitude (N <= 1024).
+// u = 2^-126 is the smallest normal fp32 number: a result below it may be flushed or lose
+// bits, an absolute error of at most u per operation, which the relative-error bound delta
+// does not cover. The thresholds keep those errors 2^12 below the quantities they touch (the
+// certificate's own slack, 3.9 against 2 sqrt 2 + 1, is 2^-5.8):
+//   E >= 2^-100      E sums 2 N <= 2^11 squares, each off by at most u: 2^-115 in all
+//   c^2 E >= 2^-114  every bound compared is at least 3.9 delta^2 >= 2^12 u, so the product D
+//                    (two roundings that can underflow) is trusted against it; delta >= 2^-57
+//                    also dwarfs the transform's summed underflow errors (< 2^15 u)
+//   E <= 2^100       E, the components (<= 2^56) and D (<= 2^113) stay finite
+//   c max(2^6, c) E <= 2^124  the bound 3.9 delta max(|component|, delta) stays finite
+// An empty range (an absurd kappa) is returned as lo = bits(1), span = 0: no frame but an
+// all-zero one is certified.
+inline void ibm_level_range(double c, uint32_t* lo_bits, uint32_t* span) {
+  auto bits = [](double x) {
+    const float f = (float)x;
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return u;
+  };
+  auto value = [](uint32_t u) {
+    float f;
+    memcpy(&f, &u, 4);
+    return (double)f;
+  };
+  double lo = 0x1p-100, hi = 0x1p100;
+  if (c > 0.0) {
+    if (0x1p-114 / (c * c) > lo) lo = 0x1p-114 / (c * c);
+    const double m = c > 64.0 ? c : 64.0;
+    if (0x1p124 / (c * m) < hi) hi = 0x1p124 / (c * m);
+  }
+  if (!(lo <= hi) || !(lo >= 0x1p-126) || !(hi <= 0x1p127)) lo = hi = 1.0;
+  uint32_t a = bits(lo), b = bits(hi);
+  if (value(a) < lo) ++a;  // lo rounded up, hi down
+  if (value(b) > hi) --b;
+  if (a > b) a = b = bits(1.0);
+  *lo_bits = a;
+  *span = b - a;
+}
 
 struct ChainArgs {
   int batch;
@@ -95,6 +143,7 @@ struct ChainArgs {
   // fp32 transform); xwin [N] the reference's fp32 Hann window, xtw [N][2] W_N^j in fp64
   // (plan tables); xstat (optional, [2]): deferred (bin, frame) decisions, exact noise ones.
   float ibm_cert;
+  uint32_t ibm_en_lo, ibm_en_span;  // the certificate's level rule (ibm_level_range)
   const float* xwin;
   const double* xtw;
   unsigned long long* xstat;

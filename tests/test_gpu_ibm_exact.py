@@ -125,6 +125,7 @@ def test_certificate_off_runs_the_fp32_decisions(avz, gpu_device):
     np.testing.assert_array_equal(cov_on[0, :, 4].cpu().numpy(), msum)
     n_off = int(np.sum(cov_off[0, :, 4].cpu().numpy() != msum))
     print(f"utterance 4242: {n_off} bins' noise counts differ without the certificate, 0 with it")
+    assert n_off > 0
 
 
 @pytest.mark.parametrize("kappa", [16.0, 1e30])
