@@ -259,6 +259,28 @@ __device__ __forceinline__ void coef_from_w(double w0r, double w0i, double w1r, 
   }
 }
 
+// det of the Hermitian [[a, b], [conj b, e]] with every product and sum rounded on its own
+// (no fma contraction): a e - (br^2 + bi^2). Fused, a e stays exact while |b|^2 is rounded,
+// so a matrix of equal entries (two identical channels at sigma = 0: a == e == br, bi == 0),
+// where LAPACK's second pivot is exactly zero and the reference takes its singular fallback,
+// would get the rounding residue of a^2 as its determinant instead of 0.
+// The five separate operations are 20 B longer than the fused three; the 11 no-ops make that
+// 64 B, so that every instruction after a solve keeps its offset within its 64-B fetch line:
+// the per-utterance synthesis kernels' loops are sensitive to it (csrc/Makefile, AVZ_ONE_TU).
+// Interleaved with the fused build at B = 256: +20 B 211.9 against 209.3 us per step (slower
+// in each of three pairs), +64 B 208.3 against 208.1 us (means of eleven pairs, run-to-run
+// spread 0.3 %).
+__device__ __forceinline__ double herm_det_d(double a, double e, double br, double bi) {
+#pragma clang fp contract(off)
+  const double ae = a * e;
+  const double rr = br * br;
+  const double ii = bi * bi;
+  const double b2 = rr + ii;
+  asm volatile("s_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\ns_nop 0\n"
+               "s_nop 0\ns_nop 0\ns_nop 0");
+  return ae - b2;
+}
+
 // Per-bin MVDR weights in fp64 (oracle_debug.py:66-79):
 //   w~ = (R/(sum m + 1e-6) + sigma I)^{-1} d ; w = w~ / (d^H w~ + 1e-10);
 //   singular -> w = [1, 0] (or ones/2, oracle_reverb.py:133-135); f < fmin -> w = 0.
@@ -275,7 +297,7 @@ __device__ __forceinline__ void mvdr_weights_d(const double (&c)[5], int k, int 
     const double nrm = c[4] + 1e-6;
     const double a = c[0] / nrm + A.sigma, e = c[1] / nrm + A.sigma;
     const double br = c[2] / nrm, bi = c[3] / nrm;
-    const double det = a * e - (br * br + bi * bi);
+    const double det = herm_det_d(a, e, br, bi);
     double t0r, t0i, t1r, t1i;
     bool solved = true;
     if (!isfinite(det)) {
