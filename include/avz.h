@@ -210,6 +210,36 @@ typedef struct avz_spectral_args {
 } avz_spectral_args;
 int avz_beamform_spectral(const avz_plan* plan, const avz_spectral_args* args, void* hip_stream);
 
+/* WPE dereverberation of a two-mic spectrum: the first stage of the reference's reverberant
+ * chain, apply_wpe's wpe(Y, taps=10, delay=3, iterations=3, psd_context=0,
+ * statistics_mode='full') call (rt_av_zoom/core/dereverb.py:76-78), as offline batch WPE
+ * (Nakatani et al. 2010; the algorithm itself is the contract). Per
+ * (item, bin), with Y [2, T] and n = 2 taps: Yt[2 tau + m, t] = Y[m, t - delay - tau] (0
+ * before the first frame); X = Y; `iterations` times p[t] = mean_m |X[m,t]|^2,
+ * lambda[t] = 1 / max(p[t], 1e-10 max_t p), R = sum_t lambda Yt Yt^H, P = sum_t lambda Yt Y^H,
+ * G = R^-1 P (fp64 sums, fp64 Cholesky), X = Y - G^H Yt; Z = X.
+ * status[b][k]: 0 = dereverberated; the other bins pass Y through unchanged: 2 where
+ * frames_b[b] - delay < 2 taps (fewer regressor frames than unknowns; decided first and by
+ * the count alone) or a Cholesky pivot is <= (2 taps + 1) 2^-52 R_jj or not finite, 1 where
+ * max_t p == 0.
+ * Y, Z: the layout of avz_beamform_spectral's Y with `bins` bins, 8-byte aligned (else
+ * AVZ_ERR_ALIGN); Z may be Y itself (same strides), no other overlap. frames_b[b] is clamped
+ * to [0, frames]; frames t >= frames_b[b] of Z are copies of Y and enter no sum.
+ * taps 1..16, delay >= 1, iterations 1..10 (else AVZ_ERR_ARG); frames 1..2048 (else
+ * AVZ_ERR_SHAPE: a problem's 24 bytes per frame and up to 16 KiB of R, P and partial sums
+ * stay in 64 KiB of LDS). No plan, no workspace, no allocation. */
+typedef struct avz_wpe_args {
+  int batch, bins, frames;      /* frames = T of the arrays                          */
+  const int* frames_b;          /* device [batch] valid frames per item, or NULL = T */
+  int taps, delay, iterations;
+  const float* Y;               /* complex64 [b][m][k][t], t contiguous; strides in complex elements */
+  long long y_stride_b, y_stride_m, y_stride_f;
+  float* Z;                     /* same layout; may alias Y exactly                  */
+  long long z_stride_b, z_stride_m, z_stride_f;
+  int* status;                  /* optional device [batch][bins]: 0, 1, 2 as above   */
+} avz_wpe_args;
+int avz_wpe_spectral(const avz_wpe_args* args, void* hip_stream);
+
 /* scipy.signal.istft(S, fs, nperseg=n_fft, noverlap=n_fft/2) of complex64 S[b][k][t]
  * (t contiguous; strides in complex elements) for `frames` frames per item: out[b] gets
  * (frames - 1) * hop samples (<= max_samples), peak-normalised per the plan; peak[b] =

@@ -41,7 +41,7 @@ EXPORTED = [
     "avz_mvdr_covariance", "avz_solve_covariance", "avz_apply_istft", "avz_beamform_spectral",
     "avz_istft", "avz_scene_generate_workspace_bytes", "avz_scene_generate",
     "avz_projection_metrics_scaled", "avz_plan_set_ibm_stats", "avz_plan_set_diagnostics",
-    "avz_ibm_window",
+    "avz_ibm_window", "avz_wpe_spectral",
 ]
 
 
@@ -82,6 +82,19 @@ class AvzSpectralArgs(ct.Structure):
         ("steer", ct.c_void_p),
         ("S", ct.c_void_p), ("s_stride_b", ct.c_longlong), ("s_stride_f", ct.c_longlong),
         ("cov_out", ct.c_void_p), ("w_out", ct.c_void_p), ("fallback", ct.c_void_p),
+    ]
+
+
+class AvzWpeArgs(ct.Structure):
+    _fields_ = [
+        ("batch", ct.c_int), ("bins", ct.c_int), ("frames", ct.c_int),
+        ("frames_b", ct.c_void_p),
+        ("taps", ct.c_int), ("delay", ct.c_int), ("iterations", ct.c_int),
+        ("Y", ct.c_void_p), ("y_stride_b", ct.c_longlong), ("y_stride_m", ct.c_longlong),
+        ("y_stride_f", ct.c_longlong),
+        ("Z", ct.c_void_p), ("z_stride_b", ct.c_longlong), ("z_stride_m", ct.c_longlong),
+        ("z_stride_f", ct.c_longlong),
+        ("status", ct.c_void_p),
     ]
 
 
@@ -127,8 +140,9 @@ def _load():
     lib.avz_beamform_spectral.argtypes = [P, ct.POINTER(AvzSpectralArgs), P]
     lib.avz_istft.argtypes = [P, ct.c_int, ct.c_int, P, ct.c_longlong, ct.c_longlong, P,
                               ct.c_longlong, P, P, ct.c_longlong, P]
+    lib.avz_wpe_spectral.argtypes = [ct.POINTER(AvzWpeArgs), P]
     for name in ("avz_mvdr_covariance", "avz_solve_covariance", "avz_apply_istft",
-                 "avz_beamform_spectral", "avz_istft"):
+                 "avz_beamform_spectral", "avz_istft", "avz_wpe_spectral"):
         getattr(lib, name).restype = ct.c_int
     lib.avz_stft.argtypes = [P, ct.c_int, ct.c_int, P, ct.c_int, P, ct.c_longlong, ct.c_longlong,
                              P, ct.c_longlong, ct.c_longlong, ct.c_longlong, P]

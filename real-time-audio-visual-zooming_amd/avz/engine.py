@@ -455,3 +455,38 @@ def srp_scan(plan: MVDRPlan, mix: torch.Tensor, lengths=None, max_len=None, n_an
                            float(angle_lo), float(angle_hi), float(f_lo), float(f_hi),
                            ct.c_void_p(out.data_ptr()), _stream_handle(stream)), "avz_srp_scan")
     return out
+
+
+def wpe_spectral(Y: torch.Tensor, taps: int = 10, delay: int = 3, iterations: int = 3,
+                 frames=None, out=None, status=None, stream=None) -> torch.Tensor:
+    """WPE dereverberation of Y [B, 2, F, T] complex64 (t contiguous) -> Z of the same shape
+    (avz_wpe_spectral; rt_av_zoom/core/dereverb.py:76-78 per item). ``frames``: optional
+    int32 [B] valid frames per item (frames beyond it are copied); ``out`` may be Y itself;
+    ``status``: optional int32 [B, F] (0 dereverberated, 1 / 2 passed through)."""
+    if Y.dtype != torch.complex64 or Y.dim() != 4 or Y.shape[1] != 2 or Y.stride(3) != 1 \
+            or not Y.is_cuda:
+        raise ValueError("Y must be complex64 [B, 2, F, T] (t contiguous) on the device")
+    B, _, F, T = Y.shape
+    if out is None:
+        out = torch.empty((B, 2, F, T), dtype=torch.complex64, device=Y.device)
+    if out.dtype != torch.complex64 or tuple(out.shape) != (B, 2, F, T) or out.stride(3) != 1 \
+            or out.device != Y.device:
+        raise ValueError("out must be complex64 [B, 2, F, T] (t contiguous) on Y's device")
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() < B
+                               or not frames.is_contiguous() or frames.device != Y.device):
+        raise ValueError("frames must be a contiguous int32 [B] tensor on Y's device")
+    if status is not None and (status.dtype != torch.int32 or status.numel() < B * F
+                               or not status.is_contiguous() or status.device != Y.device):
+        raise ValueError("status must be a contiguous int32 [B, F] tensor on Y's device")
+    a = _lib.AvzWpeArgs()
+    a.batch, a.bins, a.frames = B, F, T
+    a.frames_b = None if frames is None else frames.data_ptr()
+    a.taps, a.delay, a.iterations = int(taps), int(delay), int(iterations)
+    a.Y = Y.data_ptr()
+    a.y_stride_b, a.y_stride_m, a.y_stride_f = Y.stride(0), Y.stride(1), Y.stride(2)
+    a.Z = out.data_ptr()
+    a.z_stride_b, a.z_stride_m, a.z_stride_f = out.stride(0), out.stride(1), out.stride(2)
+    a.status = None if status is None else status.data_ptr()
+    with torch.cuda.device(Y.device):
+        check(lib.avz_wpe_spectral(ct.byref(a), _stream_handle(stream)), "avz_wpe_spectral")
+    return out

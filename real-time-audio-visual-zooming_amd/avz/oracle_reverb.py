@@ -5,8 +5,9 @@
 ``args.sigma`` (diagonal loading, :124) and ``args.hp`` (high-pass cutoff, :116) and the
 ideal-ratio-mask post-filter (:143-156) in one ``avz_mvdr_batch`` call
 (AVZ_MASK_IBM + AVZ_PF_IRM, singular bins -> ones/2 as :133-135, s /= max|s| + 1e-9 as
-:164) and writes ``output_oracle_reverb.wav`` (:170-172). Producing mixture_wpe.wav
-(WPE dereverberation, rt_av_zoom/core/dereverb.py) is out of scope.
+:164) and writes ``output_oracle_reverb.wav`` (:170-172). ``mixture_wpe.wav`` is what
+``avz.dereverb.main`` writes from ``mixture.wav`` (WPE dereverberation on the same engine,
+the mirror of rt_av_zoom/core/dereverb.py).
 """
 from __future__ import annotations
 

@@ -607,6 +607,46 @@ extern "C" int avz_beamform_spectral(const avz_plan* p, const avz_spectral_args*
   return hip_rc(avz_launch_spectral(c.n_fft, &s, &k, stream));
 }
 
+extern "C" int avz_wpe_spectral(const avz_wpe_args* a, void* stream) {
+  if (!a) return AVZ_ERR_ARG;
+  if (a->taps < 1 || a->taps > 16 || a->delay < 1 || a->iterations < 1 || a->iterations > 10)
+    return AVZ_ERR_ARG;
+  if (a->batch < 0 || a->bins < 0 || a->frames < 1 || a->frames > avz_wpe_max_frames())
+    return AVZ_ERR_SHAPE;
+  if (a->batch == 0 || a->bins == 0) return AVZ_OK;
+  if (!a->Y || !a->Z) return AVZ_ERR_ARG;
+  if (misaligned(a->Y, 8) || misaligned(a->Z, 8) || misaligned(a->frames_b, 4) ||
+      misaligned(a->status, 4))
+    return AVZ_ERR_ALIGN;
+  // Z may be Y itself (same layout); any other overlap is the caller's error
+  if (a->Z == a->Y && (a->z_stride_b != a->y_stride_b || a->z_stride_m != a->y_stride_m ||
+                       a->z_stride_f != a->y_stride_f))
+    return AVZ_ERR_ARG;
+  if (a->y_stride_f < a->frames || a->y_stride_m < (long long)a->bins * a->y_stride_f ||
+      a->z_stride_f < a->frames || a->z_stride_m < (long long)a->bins * a->z_stride_f)
+    return AVZ_ERR_SHAPE;
+  if (a->batch > 1 && (a->y_stride_b < 2 * a->y_stride_m || a->z_stride_b < 2 * a->z_stride_m))
+    return AVZ_ERR_SHAPE;
+  avz::WpeArgs w{};
+  w.batch = a->batch;
+  w.bins = a->bins;
+  w.frames = a->frames;
+  w.frames_b = a->frames_b;
+  w.taps = a->taps;
+  w.delay = a->delay;
+  w.iterations = a->iterations;
+  w.Y = a->Y;
+  w.y_sb = a->y_stride_b;
+  w.y_sm = a->y_stride_m;
+  w.y_sf = a->y_stride_f;
+  w.Z = a->Z;
+  w.z_sb = a->z_stride_b;
+  w.z_sm = a->z_stride_m;
+  w.z_sf = a->z_stride_f;
+  w.status = a->status;
+  return hip_rc(avz_launch_wpe(&w, stream));
+}
+
 extern "C" int avz_solve_covariance(const avz_plan* p, int batch, const double* cov, float* w,
                                     const double* steer, int* fallback, void* stream) {
   if (!p) return AVZ_ERR_ARG;

@@ -183,6 +183,18 @@ struct SpecArgs {
   int* flag;                  // [B] item-level fallback flags (zeroed by the launcher)
 };
 
+// WPE dereverberation of a two-mic spectrum (avz_wpe_spectral, avz_wpe.hip).
+struct WpeArgs {
+  int batch, bins, frames;
+  const int* frames_b;        // [B] valid frames per item (clamped to [0, frames]) or null
+  int taps, delay, iterations;
+  const float* Y;             // complex64 Y[b][m][k][t], m = 0, 1 (t contiguous)
+  long long y_sb, y_sm, y_sf; // complex elements
+  float* Z;                   // same layout; may be Y itself
+  long long z_sb, z_sm, z_sf;
+  int* status;                // [B][bins] or null
+};
+
 struct StftArgs {
   int batch, channels;        // channels 1 or 2
   const int* len;             // clamped to max_len in the kernel
@@ -283,6 +295,8 @@ int avz_launch_apply_istft(int n_fft, const avz::ChainArgs* a, const float* w, v
 int avz_launch_istft(int n_fft, const avz::ChainArgs* a, void* stream);
 int avz_launch_spectral(int n_fft, const avz::SpecArgs* s, const avz::ChainArgs* p, void* stream);
 int avz_launch_solve_cov(int n_fft, const avz::SpecArgs* s, const avz::ChainArgs* p, void* stream);
+int avz_wpe_max_frames(void);
+int avz_launch_wpe(const avz::WpeArgs* a, void* stream);
 int avz_launch_srp(int n_fft, const avz::ChainArgs* a, const avz::SrpArgs* s, void* stream);
 int avz_chunk_frames(void);
 int avz_launch_stft(int n_fft, const avz::StftArgs* a, void* stream);
