@@ -393,6 +393,59 @@ int avz_scene_generate(int batch, long long start_idx, int n_interferers, int n,
                        float* itf, long long ref_stride, void* workspace,
                        long long workspace_bytes, void* hip_stream);
 
+/* Reverberant shoebox scenes: the `reverb` mode of the reference's scene builders
+ * (Final_pipeline/src/simulation.py:105-165, rt_av_zoom/core/world.py:125-190), which build a
+ * pyroomacoustics ShoeBox and convolve every source with its room impulse response (RIR).
+ * The contract here is the classic image-source model (Allen & Berkley 1979), not
+ * pyroomacoustics' bits (avz/synth.py room_rir is the restatement):
+ * one energy absorption for all six walls (beta = sqrt(1 - absorption)); images q with
+ * |qx| + |qy| + |qz| <= max_order; per image the amplitude beta^order / (4 pi d), the delay
+ * d fs / c and an 81-tap Hann-windowed sinc centred on the continuous delay. No air
+ * absorption, scattering, ray tracing, RIR high-pass filter or per-wall materials. */
+typedef struct avz_room {
+  double dim[3];      /* shoebox edges, m (world.py:22) */
+  double absorption;  /* energy absorption of all six walls, 0 < a <= 1 */
+  int max_order;      /* 0 .. 20 */
+  double mic[2][3];   /* inside the room */
+  double c_sound, fs;
+} avz_room;
+
+/* Samples per RIR, floor(fs / c * Dmax) + 42 with Dmax the largest image distance bound, or
+ * a negative AVZ_ERR_* code (AVZ_ERR_ARG: invalid room; AVZ_ERR_SHAPE: more than 8192). */
+int avz_room_rir_len(const avz_room* room);
+
+/* Stage export: rir[b][s][mic][rir_len] as fp64 from src_pos[b][s][3] (device arrays).
+ * Results are bit-identical from call to call. */
+int avz_room_rir(const avz_room* room, int batch, int n_src, const double* src_pos,
+                 double* rir, void* hip_stream);
+
+/* avz_scene_mix in the room: source s of utterance b sits at src_pos[b][s][3] (device,
+ * fp64) and reaches mic c as fftconvolve(src, rir)[:n]; then avz_scene_mix's SIR gain, AWGN
+ * and shared peak. tgt / itf are the reverberant mic-1 images. The geometry, fs and c come
+ * from `room`. n >= 2, odd included. `workspace` holds avz_scene_reverb_workspace_bytes()
+ * bytes: 32 (ceil(n_src / 2) + n_src) Lc per utterance, Lc the smallest length 2^a 3^b 5^c
+ * >= n + rir_len - 1 (13.3 MB for 4 s, 4 sources, max_order 15 in the reference room). */
+long long avz_scene_reverb_workspace_bytes(const avz_room* room, int batch, int n_src, int n);
+int avz_scene_reverb_mix(const avz_room* room, int batch, int n_src, int n, const float* src,
+                         const double* src_pos, const float* noise, double sir_db,
+                         double snr_db, float* mix, long long mix_stride, long long ch_stride,
+                         float* tgt, float* itf, long long ref_stride, void* workspace,
+                         long long workspace_bytes, void* hip_stream);
+
+/* avz_scene_generate in the room: its sources and noise (the same Philox draws), source 0
+ * at target_pos, source 1 at interferer_pos (host arrays, inside the room), sources s >= 2
+ * at (1 + u0 (dim_x - 2), 1 + u1 (dim_y - 2), target_pos[2]) with u0, u1 the utterance's
+ * uniform draws 0x2000 + 2 (s - 2) + {0, 1} (simulation.py:133-136); more than one
+ * interferer needs dim_x, dim_y > 2 m. synth.make_reverb_scene_philox is the restatement. */
+long long avz_scene_reverb_generate_workspace_bytes(const avz_room* room, int batch,
+                                                    int n_interferers, int n);
+int avz_scene_reverb_generate(const avz_room* room, int batch, long long start_idx,
+                              int n_interferers, int n, unsigned seed, const double* target_pos,
+                              const double* interferer_pos, double sir_db, double snr_db,
+                              float* mix, long long mix_stride, long long ch_stride, float* tgt,
+                              float* itf, long long ref_stride, void* workspace,
+                              long long workspace_bytes, void* hip_stream);
+
 const char* avz_strerror(int code);
 /* Last HIP error string recorded by the library on this thread (diagnostics). */
 const char* avz_last_hip_error(void);

@@ -42,6 +42,9 @@ EXPORTED = [
     "avz_istft", "avz_scene_generate_workspace_bytes", "avz_scene_generate",
     "avz_projection_metrics_scaled", "avz_plan_set_ibm_stats", "avz_plan_set_diagnostics",
     "avz_ibm_window", "avz_wpe_spectral",
+    "avz_room_rir_len", "avz_room_rir", "avz_scene_reverb_workspace_bytes",
+    "avz_scene_reverb_mix", "avz_scene_reverb_generate_workspace_bytes",
+    "avz_scene_reverb_generate",
 ]
 
 
@@ -95,6 +98,13 @@ class AvzWpeArgs(ct.Structure):
         ("Z", ct.c_void_p), ("z_stride_b", ct.c_longlong), ("z_stride_m", ct.c_longlong),
         ("z_stride_f", ct.c_longlong),
         ("status", ct.c_void_p),
+    ]
+
+
+class AvzRoom(ct.Structure):
+    _fields_ = [
+        ("dim", ct.c_double * 3), ("absorption", ct.c_double), ("max_order", ct.c_int),
+        ("mic", (ct.c_double * 3) * 2), ("c_sound", ct.c_double), ("fs", ct.c_double),
     ]
 
 
@@ -167,6 +177,20 @@ def _load():
     lib.avz_scene_generate_workspace_bytes.restype = LL
     lib.avz_scene_generate.argtypes = [I, LL, I, I, ct.c_uint, D, D, D, D, D, P, LL, LL, P, P, LL,
                                        P, LL, P]
+    R = ct.POINTER(AvzRoom)
+    DP = ct.POINTER(ct.c_double)
+    lib.avz_room_rir_len.argtypes = [R]
+    lib.avz_room_rir.argtypes = [R, I, I, P, P, P]
+    lib.avz_scene_reverb_workspace_bytes.argtypes = [R, I, I, I]
+    lib.avz_scene_reverb_workspace_bytes.restype = LL
+    lib.avz_scene_reverb_mix.argtypes = [R, I, I, I, P, P, P, D, D, P, LL, LL, P, P, LL, P, LL, P]
+    lib.avz_scene_reverb_generate_workspace_bytes.argtypes = [R, I, I, I]
+    lib.avz_scene_reverb_generate_workspace_bytes.restype = LL
+    lib.avz_scene_reverb_generate.argtypes = [R, I, LL, I, I, ct.c_uint, DP, DP, D, D, P, LL, LL,
+                                              P, P, LL, P, LL, P]
+    for name in ("avz_room_rir_len", "avz_room_rir", "avz_scene_reverb_mix",
+                 "avz_scene_reverb_generate"):
+        getattr(lib, name).restype = ct.c_int
     lib.avz_strerror.argtypes = [ct.c_int]
     lib.avz_strerror.restype = ct.c_char_p
     lib.avz_last_hip_error.restype = ct.c_char_p

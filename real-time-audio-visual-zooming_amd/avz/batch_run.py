@@ -107,9 +107,13 @@ def gpu_enhancer(n_fft=1024, sigma=1.0, mic_d=0.01, max_batch=256, max_samples=6
 def run_batch(n_runs: int, start_idx: int = 0, n_interferers: int = 2, *,
               seconds: float = 4.0, batch: int = 256, device=None,
               enhance: Callable | None = None, csv_path: str | None = None,
-              scenes: str = "philox") -> BatchResult:
+              scenes: str = "philox", reverb: bool = False,
+              max_order: int = 15) -> BatchResult:
     """batch_run.run_batch equivalent over a device batch, sharded over the group.
-    scenes: "philox" (device generator; host restatement on CPU) or "host" (make_batch)."""
+    scenes: "philox" (device generator; host restatement on CPU) or "host" (make_batch).
+    reverb: the scenes of generate_scene(reverb=True) (simulation.py:105-165): the
+    reference shoebox room with image sources up to max_order (synth.Room,
+    make_reverb_batch_device; on CPU the host restatement) in place of the anechoic model."""
     rank, world = world_info()
     lo, hi = shard(n_runs, rank, world)
     dev = torch.device(device) if device is not None else (
@@ -122,7 +126,19 @@ def run_batch(n_runs: int, start_idx: int = 0, n_interferers: int = 2, *,
     sums = torch.zeros(6, dtype=torch.float64, device=dev)
     for c0 in range(start_idx + lo, start_idx + hi, batch):
         nb = min(batch, start_idx + hi - c0)
-        if scenes == "philox" and dev.type == "cuda":
+        if reverb and dev.type == "cuda":
+            d_mix, d_tgt, d_itf = synth.make_reverb_batch_device(
+                nb, start=c0, n_samples=S, n_interferers=n_interferers,
+                room=synth.Room(max_order=max_order), device=dev,
+                rng="philox" if scenes == "philox" else "host")
+        elif reverb:
+            if scenes != "philox":
+                raise ValueError("reverberant scenes on the CPU come from the Philox restatement")
+            mix, tgt, itf = synth.make_reverb_batch_philox(
+                nb, start=c0, n_samples=S, n_interferers=n_interferers,
+                room=synth.Room(max_order=max_order))
+            d_mix, d_tgt, d_itf = (torch.from_numpy(a).to(dev) for a in (mix, tgt, itf))
+        elif scenes == "philox" and dev.type == "cuda":
             d_mix, d_tgt, d_itf = synth.make_batch_device(nb, start=c0, n_samples=S,
                                                           n_interferers=n_interferers,
                                                           device=dev, rng="philox")

@@ -490,3 +490,32 @@ def wpe_spectral(Y: torch.Tensor, taps: int = 10, delay: int = 3, iterations: in
     with torch.cuda.device(Y.device):
         check(lib.avz_wpe_spectral(ct.byref(a), _stream_handle(stream)), "avz_wpe_spectral")
     return out
+
+
+def room_rir(room, src_pos, device=None, out=None, stream=None) -> torch.Tensor:
+    """Image-source RIRs of a shoebox room (avz_room_rir; synth.room_rir is the host
+    restatement): src_pos [B, S, 3] (metres; array or fp64 device tensor) -> fp64
+    [B, S, 2, rir_len], one RIR per (utterance, source, mic). ``room``: synth.Room."""
+    import numpy as np
+
+    from .synth import _room_struct
+    r = _room_struct(room)
+    L = check(lib.avz_room_rir_len(ct.byref(r)), "avz_room_rir_len")
+    if not isinstance(src_pos, torch.Tensor):
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        src_pos = torch.as_tensor(np.asarray(src_pos, np.float64)).to(dev)
+    if src_pos.dtype != torch.float64 or src_pos.dim() != 3 or src_pos.shape[2] != 3 \
+            or not src_pos.is_cuda:
+        raise ValueError("src_pos must be float64 [B, S, 3] on the device")
+    src_pos = src_pos.contiguous()
+    B, S, _ = src_pos.shape
+    if out is None:
+        out = torch.empty((B, S, 2, L), dtype=torch.float64, device=src_pos.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (B, S, 2, L) or not out.is_contiguous() \
+            or out.device != src_pos.device:
+        raise ValueError("out must be contiguous float64 [B, S, 2, rir_len] on src_pos's device")
+    with torch.cuda.device(src_pos.device):
+        check(lib.avz_room_rir(ct.byref(r), B, S, ct.c_void_p(src_pos.data_ptr()),
+                               ct.c_void_p(out.data_ptr()), _stream_handle(stream)),
+              "avz_room_rir")
+    return out

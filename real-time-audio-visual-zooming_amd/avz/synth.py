@@ -167,6 +167,7 @@ def scene_draws(idx: int, n_samples: int = 64000, n_interferers: int = 1, fs: in
 SCENE_KEY = 0x5CE7E5ED
 STREAM_NOISE, STREAM_UNIF = 0x100, 0x200
 UNIF_PHASE, UNIF_KEEP = 0x1000, 0x100000
+UNIF_POS = 0x2000  # + 2 (source - 2) + {0, 1}: room position x, y of interferers 2..
 _M32 = np.uint64(0xFFFFFFFF)
 
 
@@ -248,6 +249,12 @@ def mix_draws(angles, srcs, z, d: float = MIC_D, sir_db: float = 0.0, snr_db: fl
         d1, d2 = far_field_delays(angles[k], d)
         int_m[0] += frac_delay(srcs[k], d1, fs)
         int_m[1] += frac_delay(srcs[k], d2, fs)
+    return _mix_images(tgt_m, int_m, K, z, sir_db, snr_db)
+
+
+def _mix_images(tgt_m, int_m, K, z, sir_db, snr_db):
+    """SIR gain on mic 1, AWGN per channel and the shared peak on per-mic target and summed
+    interference images (simulation.py:167-202)."""
     p_t, p_i = np.mean(tgt_m[0] ** 2), np.mean(int_m[0] ** 2)
     if K > 0 and p_i > 0:
         g = np.sqrt(p_t / (p_i * 10 ** (sir_db / 10)))
@@ -342,4 +349,300 @@ def make_batch(batch: int, start: int = 0, n_samples: int = 64000, n_interferers
     itf = np.empty((batch, n_samples), np.float32)
     for b in range(batch):
         mix[b], tgt[b], itf[b] = make_scene(start + b, n_samples, n_interferers, **kw)
+    return mix, tgt, itf
+
+
+# ---------------------------------------------------------------- reverberant shoebox rooms
+# The `reverb` mode of the reference's scene builders (Final_pipeline/src/simulation.py:105-
+# 165, rt_av_zoom/core/world.py:125-190) builds a pyroomacoustics ShoeBox; pyroomacoustics is
+# not installed where this project is built or tested, so the contract is the classic
+# image-source model (Allen & Berkley 1979) as stated here, and avz_room_rir /
+# avz_scene_reverb_mix / avz_scene_reverb_generate (csrc/avz_scene.hip) compute this
+# arithmetic. Not modelled: air absorption, scattering or ray tracing, any RIR high-pass
+# filter, per-wall materials.
+ROOM_DIM = [4.9, 4.9, 4.9]                          # world.py:22
+RT60_TARGET = 0.5                                   # world.py:23
+MIC_LOCS = [[2.41, 2.45, 1.5], [2.49, 2.45, 1.5]]   # world.py:28-31, one row per mic
+SOURCE_TARGET_POS = [2.45, 3.45, 1.5]               # world.py:33 (90 degrees)
+SOURCE_INTERF_POS = [3.22, 3.06, 1.5]               # world.py:34 (40 degrees)
+RIR_HALF = 40                                       # taps floor(tau) - 40 .. floor(tau) + 40
+RIR_MAX = 8192
+
+
+def inverse_sabine(rt60: float, dim, c: float = C_SOUND) -> float:
+    """Energy absorption of all six walls for a Sabine reverberation time rt60:
+    24 ln 10 V / (c S rt60)."""
+    lx, ly, lz = (float(v) for v in dim)
+    V, S = lx * ly * lz, 2.0 * (lx * ly + ly * lz + lx * lz)
+    return 24.0 * np.log(10.0) * V / (c * S * rt60)
+
+
+class Room:
+    """A shoebox room with two mics (avz_room). Defaults: the reference room."""
+
+    def __init__(self, dim=None, absorption=None, max_order: int = 15, mic=None,
+                 c: float = C_SOUND, fs: float = FS):
+        self.dim = [float(v) for v in (ROOM_DIM if dim is None else dim)]
+        self.absorption = float(inverse_sabine(RT60_TARGET, self.dim, c) if absorption is None
+                                else absorption)
+        self.max_order = int(max_order)
+        self.mic = [[float(v) for v in m] for m in (MIC_LOCS if mic is None else mic)]
+        self.c, self.fs = float(c), float(fs)
+
+    @property
+    def rir_len(self) -> int:
+        return room_rir_len(self.dim, self.max_order, self.fs, self.c)
+
+
+def room_images(order: int) -> np.ndarray:
+    """The image triples q, |qx| + |qy| + |qz| <= order, as int [count, 3] in the order the
+    RIR sums them: qx, then qy, then qz ascending. count = (2N + 1)(2N^2 + 2N + 3) / 3."""
+    out = []
+    for qx in range(-order, order + 1):
+        rx = order - abs(qx)
+        for qy in range(-rx, rx + 1):
+            rz = rx - abs(qy)
+            out.extend((qx, qy, qz) for qz in range(-rz, rz + 1))
+    return np.array(out, dtype=np.int64).reshape(-1, 3)
+
+
+def room_rir_len(dim, max_order: int, fs: float = FS, c: float = C_SOUND) -> int:
+    """floor(fs / c * Dmax) + 42, Dmax = max over axes a of sqrt(((N + 1) L_a)^2 + sum of
+    the other L_o^2): a bound on every image distance (the squared distance is convex in the
+    per-axis image counts), plus the 40 taps after floor(tau) and one sample of slack."""
+    dim = [float(v) for v in dim]
+    dmax = 0.0
+    for a in range(3):
+        q = (max_order + 1) * dim[a]
+        q *= q
+        for o in range(3):
+            if o != a:
+                q += dim[o] * dim[o]
+        dmax = max(dmax, np.sqrt(q))
+    return int(np.floor(fs / c * dmax)) + 42
+
+
+def frac_delay_taps(tau, amp=1.0, dtype=np.float64):
+    """The 81 taps of one image: (n, amp * w(n - tau) * sinc(n - tau)) at n = floor(tau) - 40
+    .. floor(tau) + 40, w(x) = 0.5 (1 + cos(2 pi x / 81)) for |x| <= 40.5, else 0: the window
+    is centred on the continuous delay, so the taps are continuous in tau. With n = floor(tau)
+    + k, sin(pi (n - tau)) = -(-1)^k sin(pi frac), frac = tau - floor(tau). tau, amp: arrays
+    [M] -> n int64 [M, 81], values [M, 81]."""
+    tau = np.atleast_1d(np.asarray(tau, dtype))
+    amp = np.broadcast_to(np.asarray(amp, dtype), tau.shape)
+    pi = 4 * np.arctan(dtype(1))
+    fl = np.floor(tau)
+    frac = tau - fl
+    k = np.arange(-RIR_HALF, RIR_HALF + 1)
+    x = k.astype(dtype)[None, :] - frac[:, None]
+    n = fl.astype(np.int64)[:, None] + k[None, :]
+    w = dtype(0.5) * (1 + np.cos(2 * pi * x / 81))
+    w = np.where(np.abs(x) <= dtype(40.5), w, dtype(0))
+    sgn = np.where(k % 2 == 0, -1.0, 1.0).astype(dtype)[None, :]
+    # sin(pi frac) as sin(pi min(frac, 1 - frac)) (1 - frac is exact): accurate to the last
+    # bits as frac -> 1, where rounding pi * frac would lose the tap's continuity
+    sp = np.sin(pi * np.where(frac > 0.5, 1 - frac, frac))[:, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sinc = np.where(x == 0, dtype(1), sgn * sp / (pi * x))
+    return n, amp[:, None] * w * sinc
+
+
+def room_rir(dim, src, mic, absorption: float, max_order: int, fs: float = FS,
+             c: float = C_SOUND, dtype=np.float64, rir_len: int | None = None) -> np.ndarray:
+    """Image-source RIR from `src` to `mic` in the shoebox `dim` (all six walls with energy
+    absorption `absorption`, beta = sqrt(1 - absorption)); every operation in `dtype`.
+    Image q along axis i sits at q L + s (q even) or (q + 1) L - s (q odd); its amplitude is
+    beta^order / (4 pi d) (the power by repeated multiplication, d clamped to >= 1e-3 m), its
+    delay tau = d fs / c samples; frac_delay_taps spreads it. Taps outside [0, rir_len) are
+    dropped; each sample sums its images in room_images order."""
+    L = room_rir_len(dim, max_order, fs, c) if rir_len is None else rir_len
+    dim, src, mic = (np.asarray(v, np.float64).astype(dtype) for v in (dim, src, mic))
+    pi = 4 * np.arctan(dtype(1))
+    q = room_images(max_order)
+    odd = (q % 2) == 1
+    img = np.where(odd, (q + 1).astype(dtype) * dim[None, :] - src[None, :],
+                   q.astype(dtype) * dim[None, :] + src[None, :])
+    dx, dy, dz = (img[:, a] - mic[a] for a in range(3))
+    d = np.maximum(np.sqrt(dx * dx + dy * dy + dz * dz), dtype(1e-3))
+    beta = np.sqrt(dtype(1) - dtype(absorption))
+    bp = np.ones(max_order + 1, dtype)
+    for o in range(1, max_order + 1):
+        bp[o] = bp[o - 1] * beta
+    amp = bp[np.abs(q).sum(axis=1)] / (4 * pi * d)
+    tau = d * dtype(fs) / dtype(c)
+    n, v = frac_delay_taps(tau, amp, dtype)
+    h = np.zeros(L, dtype)
+    ok = (n >= 0) & (n < L)
+    np.add.at(h, n[ok], v[ok])  # unbuffered, in index order: image by image
+    return h
+
+
+def room_rirs(room: Room, positions, dtype=np.float64) -> np.ndarray:
+    """[S, 2, rir_len]: the RIRs from positions [S, 3] to the room's two mics."""
+    return np.stack([np.stack([room_rir(room.dim, p, m, room.absorption, room.max_order,
+                                        room.fs, room.c, dtype) for m in room.mic])
+                     for p in np.asarray(positions, np.float64).reshape(-1, 3)])
+
+
+def reverb_mix_draws(positions, srcs, z, room: Room | None = None, sir_db: float = 0.0,
+                     snr_db: float = 5.0):
+    """mix_draws in a room: source s at positions[s] reaches mic c as fftconvolve(src,
+    rir)[:n] (simulation.py:143-165); then the same SIR gain, AWGN and shared peak. Returns
+    (mix [2, S], tgt, itf) float32; tgt / itf are the reverberant mic-1 images."""
+    from scipy.signal import fftconvolve
+    room = room or Room()
+    srcs = np.asarray(srcs, np.float64)
+    n = srcs.shape[-1]
+    K = srcs.shape[0] - 1
+    h = room_rirs(room, positions)
+    tgt_m = [fftconvolve(srcs[0], h[0, c])[:n] for c in range(2)]
+    int_m = [np.zeros(n), np.zeros(n)]
+    for k in range(1, K + 1):
+        for c in range(2):
+            int_m[c] += fftconvolve(srcs[k], h[k, c])[:n]
+    return _mix_images(tgt_m, int_m, K, z, sir_db, snr_db)
+
+
+def room_positions_philox(key, n_interferers: int, room: Room, target_pos=None,
+                          interferer_pos=None) -> np.ndarray:
+    """[1 + K, 3]: the target, interferer 1, and interferers s >= 2 at (1 + u0 (dim_x - 2),
+    1 + u1 (dim_y - 2), target z) with u = philox_uniform(key, UNIF_POS + 2 (s - 2) + {0, 1})
+    (simulation.py:133-136 draws them in [1, dim - 1])."""
+    t = SOURCE_TARGET_POS if target_pos is None else target_pos
+    i = SOURCE_INTERF_POS if interferer_pos is None else interferer_pos
+    pos = [list(map(float, t)), list(map(float, i))][:1 + n_interferers]
+    for s in range(2, 1 + n_interferers):
+        u = philox_uniform(key, UNIF_POS + 2 * (s - 2) + np.arange(2))
+        pos.append([1.0 + u[0] * (room.dim[0] - 2.0), 1.0 + u[1] * (room.dim[1] - 2.0),
+                    float(t[2])])
+    return np.array(pos, np.float64).reshape(-1, 3)
+
+
+def reverb_scene_draws_philox(idx: int, n_samples: int = 64000, n_interferers: int = 1,
+                              room: Room | None = None, seed: int = 0, target_pos=None,
+                              interferer_pos=None):
+    """(positions [1 + K, 3], sources [1 + K, S], unit-normal noise [2, S]) of utterance idx:
+    scene_draws_philox's sources and noise, positions in place of the azimuths."""
+    room = room or Room()
+    _, srcs, z = scene_draws_philox(idx, n_samples, n_interferers, room.fs, seed)
+    pos = room_positions_philox(_key(idx, seed), n_interferers, room, target_pos, interferer_pos)
+    return pos, srcs, z
+
+
+def make_reverb_scene_philox(idx: int, n_samples: int = 64000, n_interferers: int = 1,
+                             room: Room | None = None, sir_db: float = 0.0, snr_db: float = 5.0,
+                             seed: int = 0, target_pos=None, interferer_pos=None):
+    """Host restatement of avz_scene_reverb_generate for one utterance."""
+    room = room or Room()
+    pos, srcs, z = reverb_scene_draws_philox(idx, n_samples, n_interferers, room, seed,
+                                             target_pos, interferer_pos)
+    return reverb_mix_draws(pos, srcs, z, room, sir_db, snr_db)
+
+
+def make_reverb_batch_philox(batch: int, start: int = 0, n_samples: int = 64000,
+                             n_interferers: int = 2, seed: int = 0, **kw):
+    mix = np.empty((batch, 2, n_samples), np.float32)
+    tgt = np.empty((batch, n_samples), np.float32)
+    itf = np.empty((batch, n_samples), np.float32)
+    for b in range(batch):
+        mix[b], tgt[b], itf[b] = make_reverb_scene_philox(start + b, n_samples, n_interferers,
+                                                          seed=seed, **kw)
+    return mix, tgt, itf
+
+
+def reverb_scene_draws(idx: int, n_samples: int = 64000, n_interferers: int = 1,
+                       room: Room | None = None, target_pos=None, interferer_pos=None):
+    """scene_draws's sources and noise (the host RNG stream of make_scene(idx)); interferers
+    2.. are placed in [1, dim - 1] on x and y by default_rng(2000 + idx), at the target's z."""
+    room = room or Room()
+    ang, srcs, z = scene_draws(idx, n_samples, n_interferers, int(room.fs))
+    t = SOURCE_TARGET_POS if target_pos is None else target_pos
+    i = SOURCE_INTERF_POS if interferer_pos is None else interferer_pos
+    pos = [list(map(float, t)), list(map(float, i))][:1 + n_interferers]
+    rng = np.random.default_rng(2000 + idx)
+    for s in range(2, 1 + n_interferers):
+        u = rng.random(2)
+        pos.append([1.0 + u[0] * (room.dim[0] - 2.0), 1.0 + u[1] * (room.dim[1] - 2.0),
+                    float(t[2])])
+    return np.array(pos, np.float64).reshape(-1, 3), srcs, z
+
+
+def _room_struct(room: Room):
+    from ._lib import AvzRoom
+    r = AvzRoom()
+    for a in range(3):
+        r.dim[a] = room.dim[a]
+        r.mic[0][a], r.mic[1][a] = room.mic[0][a], room.mic[1][a]
+    r.absorption, r.max_order, r.c_sound, r.fs = room.absorption, room.max_order, room.c, room.fs
+    return r
+
+
+REVERB_SLICE_BYTES = 1 << 30  # workspace per call of make_reverb_batch_device
+
+
+def make_reverb_batch_device(batch: int, start: int = 0, n_samples: int = 64000,
+                             n_interferers: int = 2, room: Room | None = None,
+                             sir_db: float = 0.0, snr_db: float = 5.0, device=None,
+                             rng: str = "host", seed: int = 0, target_pos=None,
+                             interferer_pos=None):
+    """make_batch_device in a room (mix [B, 2, S], tgt [B, S], itf [B, S] device tensors).
+
+    rng="host":   the host draws the sources and noise (reverb_scene_draws) and
+                  avz_scene_reverb_mix does the RIRs, the convolutions and the mixing
+                  (reverb_mix_draws is the restatement).
+    rng="philox": avz_scene_reverb_generate, everything on the device
+                  (make_reverb_batch_philox is the restatement).
+    The workspace is 32 (ceil(S / 2) + S) Lc bytes per utterance for S sources (13.3 MB at
+    4 s, 4 sources, max_order 15), so the batch runs in slices of at most REVERB_SLICE_BYTES
+    of workspace; the scenes do not depend on the slicing."""
+    import ctypes as ct
+
+    import torch
+
+    from ._lib import check, lib
+    from .engine import _stream_handle
+    room = room or Room()
+    dev = device or torch.device("cuda", torch.cuda.current_device())
+    K, n = n_interferers, n_samples
+    if rng not in ("host", "philox"):
+        raise ValueError(f"rng must be 'host' or 'philox', not {rng!r}")
+    r = _room_struct(room)
+    mix = torch.empty((batch, 2, n), dtype=torch.float32, device=dev)
+    tgt = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    itf = torch.empty((batch, n), dtype=torch.float32, device=dev)
+    if batch == 0:
+        return mix, tgt, itf
+    p = lambda t: ct.c_void_p(t.data_ptr())  # noqa: E731
+    ws_fn = (lib.avz_scene_reverb_generate_workspace_bytes if rng == "philox"
+             else lib.avz_scene_reverb_workspace_bytes)
+    cnt = K if rng == "philox" else 1 + K
+    check(lib.avz_room_rir_len(ct.byref(r)), "avz_room_rir_len")
+    per = ws_fn(ct.byref(r), 1, cnt, n)
+    step = max(1, min(batch, REVERB_SLICE_BYTES // max(per, 1)))
+    ws_bytes = ws_fn(ct.byref(r), step, cnt, n)
+    ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
+    D3 = ct.c_double * 3
+    tp = D3(*(SOURCE_TARGET_POS if target_pos is None else target_pos))
+    ip = D3(*(SOURCE_INTERF_POS if interferer_pos is None else interferer_pos))
+    with torch.cuda.device(dev):
+        for b0 in range(0, batch, step):
+            nb = min(step, batch - b0)
+            m, t, i = mix[b0:b0 + nb], tgt[b0:b0 + nb], itf[b0:b0 + nb]
+            if rng == "philox":
+                check(lib.avz_scene_reverb_generate(
+                    ct.byref(r), nb, start + b0, K, n, seed, tp, ip, sir_db, snr_db, p(m),
+                    mix.stride(0), mix.stride(1), p(t), p(i), tgt.stride(0), p(ws), ws_bytes,
+                    _stream_handle(None)), "avz_scene_reverb_generate")
+                continue
+            pos = np.empty((nb, 1 + K, 3))
+            srcs = np.empty((nb, 1 + K, n), np.float32)
+            noise = np.empty((nb, 2, n), np.float32)
+            for b in range(nb):
+                pos[b], srcs[b], noise[b] = reverb_scene_draws(start + b0 + b, n, K, room,
+                                                               target_pos, interferer_pos)
+            d_pos, d_src, d_noise = (torch.from_numpy(a).to(dev) for a in (pos, srcs, noise))
+            check(lib.avz_scene_reverb_mix(
+                ct.byref(r), nb, 1 + K, n, p(d_src), p(d_pos), p(d_noise), sir_db, snr_db, p(m),
+                mix.stride(0), mix.stride(1), p(t), p(i), tgt.stride(0), p(ws), ws_bytes,
+                _stream_handle(None)), "avz_scene_reverb_mix")
     return mix, tgt, itf

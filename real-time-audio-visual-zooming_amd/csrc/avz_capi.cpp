@@ -881,8 +881,9 @@ extern "C" long long avz_scene_workspace_bytes(int batch, int n_src, int n) {
 
 static int scene_check(int batch, int n_src, int n, double fs, double c_sound, float* mix,
                        long long mix_stride, long long ch_stride, float* tgt, float* itf,
-                       long long ref_stride, void* workspace) {
-  if (batch < 0 || n_src < 1 || n < 2 || (n & 1)) return AVZ_ERR_SHAPE;  // irfft pairs: n even
+                       long long ref_stride, void* workspace, bool even = true) {
+  // irfft pairs: n even on the anechoic paths
+  if (batch < 0 || n_src < 1 || n < 2 || (even && (n & 1))) return AVZ_ERR_SHAPE;
   if (batch == 0) return AVZ_OK;
   if (!mix || !tgt || !itf || !workspace) return AVZ_ERR_ARG;
   if (!(fs > 0) || !(c_sound > 0)) return AVZ_ERR_ARG;
@@ -967,6 +968,134 @@ extern "C" int avz_scene_generate(int batch, long long start_idx, int n_interfer
   avz::SceneArgs s = scene_args(batch, n_src, n, mic_d, c_sound, fs, sir_db, snr_db, mix,
                                 mix_stride, ch_stride, tgt, itf, ref_stride);
   const int rc = avz_launch_scene_generate(&s, start_idx, seed, workspace, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+// ---------------------------------------------------------------- shoebox rooms
+constexpr int kRoomMaxOrder = 20;
+constexpr int kRoomMaxRir = 8192;  // one fp64 RIR in 64 KiB of LDS (avz_room_rir_kernel)
+
+// Validates `room` on the host and fills the kernels' argument block.
+static int room_check(const avz_room* room, avz::RoomArgs* r) {
+  if (!room) return AVZ_ERR_ARG;
+  auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+  if (!pos(room->fs) || !pos(room->c_sound)) return AVZ_ERR_ARG;
+  if (!(room->absorption > 0.0 && room->absorption <= 1.0)) return AVZ_ERR_ARG;
+  if (room->max_order < 0 || room->max_order > kRoomMaxOrder) return AVZ_ERR_ARG;
+  for (int a = 0; a < 3; ++a) {
+    if (!pos(room->dim[a])) return AVZ_ERR_ARG;
+    for (int m = 0; m < 2; ++m)
+      if (!(room->mic[m][a] >= 0.0 && room->mic[m][a] <= room->dim[a])) return AVZ_ERR_ARG;
+  }
+  const long long len = avz_room_rir_samples(room->dim, room->max_order, room->fs, room->c_sound);
+  if (len > kRoomMaxRir) return AVZ_ERR_SHAPE;
+  for (int a = 0; a < 3; ++a) {
+    r->dim[a] = room->dim[a];
+    r->mic[0][a] = room->mic[0][a];
+    r->mic[1][a] = room->mic[1][a];
+  }
+  r->beta = std::sqrt(1.0 - room->absorption);
+  r->c_sound = room->c_sound;
+  r->fs = room->fs;
+  r->max_order = room->max_order;
+  r->rir_len = (int)len;
+  return AVZ_OK;
+}
+
+extern "C" int avz_room_rir_len(const avz_room* room) {
+  avz::RoomArgs r{};
+  const int rc = room_check(room, &r);
+  return rc != AVZ_OK ? rc : r.rir_len;
+}
+
+extern "C" int avz_room_rir(const avz_room* room, int batch, int n_src, const double* src_pos,
+                            double* rir, void* stream) {
+  avz::RoomArgs r{};
+  const int rc0 = room_check(room, &r);
+  if (rc0 != AVZ_OK) return rc0;
+  if (batch < 0 || n_src < 1) return AVZ_ERR_SHAPE;
+  if (batch == 0) return AVZ_OK;
+  if (!src_pos || !rir) return AVZ_ERR_ARG;
+  if (2LL * batch * n_src > 0x7fffffffLL) return AVZ_ERR_UNSUPPORTED;  // grid.x
+  const int rc = avz_launch_room_rir(&r, batch, n_src, src_pos, rir, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+// n + rir_len - 1 and the smooth length above it stay far inside int
+constexpr int kRoomMaxSamples = 1 << 28;
+
+extern "C" long long avz_scene_reverb_workspace_bytes(const avz_room* room, int batch, int n_src,
+                                                      int n) {
+  avz::RoomArgs r{};
+  if (room_check(room, &r) != AVZ_OK || batch <= 0 || n_src <= 0 || n <= 0 || n > kRoomMaxSamples)
+    return 0;
+  return avz_scene_reverb_ws(&r, batch, n_src, n);
+}
+
+extern "C" int avz_scene_reverb_mix(const avz_room* room, int batch, int n_src, int n,
+                                    const float* src, const double* src_pos, const float* noise,
+                                    double sir_db, double snr_db, float* mix, long long mix_stride,
+                                    long long ch_stride, float* tgt, float* itf,
+                                    long long ref_stride, void* workspace,
+                                    long long workspace_bytes, void* stream) {
+  avz::RoomArgs r{};
+  const int rc1 = room_check(room, &r);
+  if (rc1 != AVZ_OK) return rc1;
+  const int rc0 = scene_check(batch, n_src, n, r.fs, r.c_sound, mix, mix_stride, ch_stride, tgt,
+                              itf, ref_stride, workspace, false);
+  if (rc0 != AVZ_OK || batch == 0) return rc0;
+  if (!src || !src_pos || !noise) return AVZ_ERR_ARG;
+  if (n > kRoomMaxSamples || n_src > 256) return AVZ_ERR_UNSUPPORTED;
+  if (workspace_bytes < avz_scene_reverb_ws(&r, batch, n_src, n)) return AVZ_ERR_SHAPE;
+  avz::SceneArgs s = scene_args(batch, n_src, n, 0.0, r.c_sound, r.fs, sir_db, snr_db, mix,
+                                mix_stride, ch_stride, tgt, itf, ref_stride);
+  s.src = src;
+  s.angles_deg = src_pos;
+  s.noise = noise;
+  const int rc = avz_launch_scene_reverb(&r, &s, workspace, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+extern "C" long long avz_scene_reverb_generate_workspace_bytes(const avz_room* room, int batch,
+                                                               int n_interferers, int n) {
+  avz::RoomArgs r{};
+  if (room_check(room, &r) != AVZ_OK || batch <= 0 || n_interferers < 0 || n <= 0 ||
+      n > kRoomMaxSamples)
+    return 0;
+  return avz_scene_reverb_gen_ws(&r, batch, 1 + n_interferers, n);
+}
+
+extern "C" int avz_scene_reverb_generate(const avz_room* room, int batch, long long start_idx,
+                                         int n_interferers, int n, unsigned seed,
+                                         const double* target_pos, const double* interferer_pos,
+                                         double sir_db, double snr_db, float* mix,
+                                         long long mix_stride, long long ch_stride, float* tgt,
+                                         float* itf, long long ref_stride, void* workspace,
+                                         long long workspace_bytes, void* stream) {
+  avz::RoomArgs r{};
+  const int rc1 = room_check(room, &r);
+  if (rc1 != AVZ_OK) return rc1;
+  if (n_interferers < 0 || start_idx < 0 || !target_pos || !interferer_pos) return AVZ_ERR_ARG;
+  if (n_interferers > kMaxInterferers || !(r.fs >= 4.0)) return AVZ_ERR_ARG;
+  // interferers 2.. are drawn in [1, dim - 1] on x and y
+  if (n_interferers > 1 && !(r.dim[0] > 2.0 && r.dim[1] > 2.0)) return AVZ_ERR_ARG;
+  for (int a = 0; a < 3; ++a)
+    if (!(target_pos[a] >= 0.0 && target_pos[a] <= r.dim[a]) ||
+        !(interferer_pos[a] >= 0.0 && interferer_pos[a] <= r.dim[a]))
+      return AVZ_ERR_ARG;
+  const int n_src = 1 + n_interferers;
+  const int rc0 = scene_check(batch, n_src, n, r.fs, r.c_sound, mix, mix_stride, ch_stride, tgt,
+                              itf, ref_stride, workspace, false);
+  if (rc0 != AVZ_OK || batch == 0) return rc0;
+  if (n > kRoomMaxSamples) return AVZ_ERR_UNSUPPORTED;
+  if (workspace_bytes < avz_scene_reverb_gen_ws(&r, batch, n_src, n)) return AVZ_ERR_SHAPE;
+  avz::SceneArgs s = scene_args(batch, n_src, n, 0.0, r.c_sound, r.fs, sir_db, snr_db, mix,
+                                mix_stride, ch_stride, tgt, itf, ref_stride);
+  const int rc = avz_launch_scene_reverb_generate(&r, &s, start_idx, seed, target_pos,
+                                                  interferer_pos, workspace, stream);
   if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
   return rc;
 }

@@ -269,9 +269,30 @@ struct SceneArgs {
   long long ref_stride;
 };
 
+// Shoebox room of the image-source scenes (avz_room, validated; avz_scene.hip).
+struct RoomArgs {
+  double dim[3];              // edges, m
+  double beta;                // wall reflection coefficient sqrt(1 - absorption)
+  double mic[2][3];
+  double c_sound, fs;
+  int max_order, rir_len;     // rir_len from avz_room_rir_samples
+};
+
 }  // namespace avz
 
 extern "C" {
+// Samples per RIR: floor(fs / c * Dmax) + 42 (may exceed the 8192 the kernel accepts).
+long long avz_room_rir_samples(const double* dim, int max_order, double fs, double c_sound);
+int avz_room_conv_len(int n, int rir_len);  // smallest 2-3-5-smooth length >= n + rir_len - 1
+int avz_launch_room_rir(const avz::RoomArgs* r, int batch, int n_src, const double* src_pos,
+                        double* rir, void* stream);
+long long avz_scene_reverb_ws(const avz::RoomArgs* r, int batch, int n_src, int n);
+// a->angles_deg carries src_pos[b][s][3] here
+int avz_launch_scene_reverb(const avz::RoomArgs* r, const avz::SceneArgs* a, void* ws, void* stream);
+long long avz_scene_reverb_gen_ws(const avz::RoomArgs* r, int batch, int n_src, int n);
+int avz_launch_scene_reverb_generate(const avz::RoomArgs* r, avz::SceneArgs* a, long long start,
+                                     uint32_t seed, const double* target_pos,
+                                     const double* interferer_pos, void* ws, void* stream);
 int avz_launch_scene(const avz::SceneArgs* a, void* ws, void* stream);
 int avz_launch_scene_generate(avz::SceneArgs* a, long long start, uint32_t seed, void* ws,
                               void* stream);

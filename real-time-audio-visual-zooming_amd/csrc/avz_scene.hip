@@ -12,6 +12,11 @@
 //                         source model with its syllabic envelope (synth.speech_like), the
 //                         interferer azimuths; synth.make_scene_philox is its host restatement.
 //
+// The reverberant counterparts (avz_room_rir, avz_scene_reverb_mix, avz_scene_reverb_generate:
+// the reference's ShoeBox scenes, simulation.py:105-165) follow the anechoic code: an
+// image-source RIR kernel and the convolution with it at a padded FFT length, into the same
+// mixing back end.
+//
 // Fractional delay, O(n log n). Real sources are packed two per complex signal, run
 // through a mixed-radix (8, 4, 2, 5, 3) Stockham FFT in fp64, split, multiplied by the
 // per-mic phase ramps exp(-2 pi i f tau) with irfft's conventions (DC and Nyquist imaginary
@@ -23,6 +28,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "avz_internal.h"
 
@@ -55,6 +61,7 @@ constexpr uint32_t kStreamNoise = 0x100u;  // + mic
 constexpr uint32_t kStreamUnif = 0x200u;
 constexpr uint32_t kUnifPhase = 0x1000u;     // + source: envelope phase
 constexpr uint32_t kUnifKeep = 0x100000u;    // * (1 + source) + block: keep flags
+constexpr uint32_t kUnifPos = 0x2000u;       // + 2 (source - 2) + {0, 1}: room position x, y
 constexpr int kSegLen = 256;                 // AR(2) segment (even: normal pairs stay whole)
 
 __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {
@@ -128,7 +135,7 @@ __global__ void __launch_bounds__(256) scene_ar_kernel(GenArgs G) {
       const double y = x[q] + 1.4 * y1 - 0.45 * y2;
       y2 = y1;
       y1 = y;
-      if (FINAL) {
+      if (FINAL && m + q < G.n) {  // odd n: the last pair's second sample falls outside
         const int mm = m + q;
         if (mm / blk != keep_blk) {
           keep_blk = mm / blk;
@@ -183,7 +190,7 @@ __global__ void __launch_bounds__(64) scene_ar_scan_kernel(GenArgs G) {
 
 __global__ void __launch_bounds__(256) scene_noise_kernel(GenArgs G) {
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int half = G.n / 2;
+  const int half = (G.n + 1) / 2;  // odd n: the last pair keeps its first normal
   if (t >= (long long)G.batch * 2 * half) return;
   const int i = (int)(t % half);
   const int c = (int)((t / half) & 1);
@@ -194,7 +201,7 @@ __global__ void __launch_bounds__(256) scene_noise_kernel(GenArgs G) {
   normal_pair(k0, k1, kStreamNoise + (uint32_t)c, (uint32_t)i, z0, z1);
   float* z = G.noise + ((long long)b * 2 + c) * G.n + 2 * i;
   z[0] = (float)z0;
-  z[1] = (float)z1;
+  if (2 * i + 1 < G.n) z[1] = (float)z1;
 }
 
 // ================================================================ mixed-radix FFT (fp64)
@@ -478,7 +485,8 @@ __global__ void __launch_bounds__(256) scene_conv_pack_kernel(SceneArgs A, doubl
 //   tgt_m = image(target), int_m = g * sum_k image(interferer k), g for SIR sir_db on mic 1;
 //   noisy = clean + sqrt(mean(clean^2) / 10^(snr/10)) * z  (world.py:93-98 add_awgn);
 //   peak = max |noisy| + 1e-9 over both mics; outputs / peak.
-// Images: ti[b][0][m] = n (T0 + i T1), ti[b][1][m] = n (I0 + i I1).
+// Images: ti[b][0][m] = nfft (T0 + i T1), ti[b][1][m] = nfft (I0 + i I1), m < n <= nfft: the
+// transform length (n on the anechoic paths, the padded length of the room convolution).
 constexpr int kMixThreads = 256;
 __device__ __forceinline__ double block_sum(double v, double* red) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -502,13 +510,13 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 }
 
 __global__ void __launch_bounds__(kMixThreads) avz_scene_mix_kernel(SceneArgs A, const double2* ti,
-                                                                    long long sb) {
+                                                                    long long sb, int nfft) {
   __shared__ double red[kMixThreads / 64];
   __shared__ float redf[kMixThreads / 64];
   const int b = blockIdx.x, tid = threadIdx.x, n = A.n, K = A.n_src - 1;
   const double2* T = ti + (long long)b * sb;
-  const double2* I = T + n;
-  const double sc = 1.0 / (double)n;
+  const double2* I = T + nfft;
+  const double sc = 1.0 / (double)nfft;
   auto tgt_img = [&](int mic, int m) -> double { return (mic ? T[m].y : T[m].x) * sc; };
   auto int_img = [&](int mic, int m) -> double { return (mic ? I[m].y : I[m].x) * sc; };
   double st = 0.0, si = 0.0;
@@ -558,6 +566,187 @@ __global__ void __launch_bounds__(kMixThreads) avz_scene_mix_kernel(SceneArgs A,
   }
 }
 
+// ================================================================ shoebox rooms
+// Image-source model (Allen & Berkley 1979) of synth.room_rir: images q, |qx| + |qy| + |qz|
+// <= max_order, in the order of synth.room_images (qx, then qy, then qz ascending); image
+// coordinate q L + s (q even) or (q + 1) L - s (q odd); amplitude beta^order / (4 pi d) with
+// beta^order by repeated multiplication; delay tau = d fs / c; 81 taps amp w(n - tau)
+// sinc(n - tau) at n = floor(tau) - 40 .. + 40, w the Hann window of width 81 centred on tau.
+constexpr int kRirHalf = 40;
+
+// Orders one wave's LDS stores before its later LDS loads across lanes.
+__device__ __forceinline__ void room_wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ double room_lane(double v, int j) {  // lane j's v (j uniform)
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), j);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), j);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double room_image_coord(int q, double L, double s) {
+#pragma clang fp contract(off)  // the host restatement's roundings
+  return (q & 1) ? (double)(q + 1) * L - s : (double)q * L + s;
+}
+
+// Where sample i of RIR (b, s, mic) goes: p[b sb + s ss + mic sm + i si] (doubles).
+struct RirOut {
+  double* p;
+  long long sb, ss;
+  int sm, si;
+};
+
+// One wave per RIR (b, s, mic), accumulated in fp64 in LDS and written once. The wave walks
+// the (qx, qy) rows; the lanes compute the row's <= 41 images (one per qz), then the images
+// go through the wave one at a time, their 81 taps on the lanes in two passes. A wave's LDS
+// operations execute in order, so every sample sums its images in room_images order on
+// every call: no atomics, no block barrier. sin(pi (n - tau)) = -(-1)^k sin(pi frac) for
+// n = floor(tau) + k, and the window's cosine comes from the lane's cos / sin(2 pi k / 81)
+// and the image's cos / sin(2 pi frac / 81): one sinpi and one sincospi per image.
+__global__ void __launch_bounds__(64) avz_room_rir_kernel(RoomArgs R, int n_src,
+                                                          const double* __restrict__ src_pos,
+                                                          RirOut O) {
+  extern __shared__ double room_h[];
+  const int lane = threadIdx.x;
+  const int mic = blockIdx.x & 1;
+  const long long bs = blockIdx.x >> 1;
+  const int L = R.rir_len, N = R.max_order;
+  for (int i = lane; i < L; i += 64) room_h[i] = 0.0;
+  room_wave_lds_sync();
+  const double sx = src_pos[bs * 3], sy = src_pos[bs * 3 + 1], sz = src_pos[bs * 3 + 2];
+  const double mx = R.mic[mic][0], my = R.mic[mic][1], mz = R.mic[mic][2];
+  double ck[2], sk[2];  // taps k = lane - 40 and lane + 24
+#pragma unroll
+  for (int t = 0; t < 2; ++t) sincospi(2.0 * (double)(lane - kRirHalf + 64 * t) / 81.0, &sk[t], &ck[t]);
+  const double sgn = (lane & 1) ? 1.0 : -1.0;  // -(-1)^k: both taps have the lane's parity
+  for (int qx = -N; qx <= N; ++qx) {
+    const int rx = N - abs(qx);
+    const double dx = room_image_coord(qx, R.dim[0], sx) - mx;
+    for (int qy = -rx; qy <= rx; ++qy) {
+      const int rz = rx - abs(qy);
+      const double dy = room_image_coord(qy, R.dim[1], sy) - my;
+      // lane l <= 2 rz: the image qz = l - rz
+      double amp, frac, sp, sf, cf;
+      int fl;
+      {
+#pragma clang fp contract(off)
+        const int qz = lane - rz;
+        const double dz = room_image_coord(qz, R.dim[2], sz) - mz;
+        const double d = fmax(sqrt(dx * dx + dy * dy + dz * dz), 1e-3);
+        double bp = 1.0;
+        for (int o = abs(qx) + abs(qy) + abs(qz); o > 0; --o) bp *= R.beta;
+        amp = bp / (4.0 * M_PI * d);
+        const double tau = d * R.fs / R.c_sound;
+        // an image past the RIR (or a non-finite source position) leaves no tap inside
+        const bool in = tau < (double)(L + kRirHalf + 1);
+        const double ft = in ? floor(tau) : 0.0;
+        fl = in ? (int)ft : -(1 << 20);
+        frac = in ? tau - ft : 0.0;
+        sp = sinpi(frac);
+        sincospi(2.0 * frac / 81.0, &sf, &cf);
+      }
+      for (int j = 0; j <= 2 * rz; ++j) {
+        const double a_j = room_lane(amp, j), f_j = room_lane(frac, j), sp_j = room_lane(sp, j);
+        const double sf_j = room_lane(sf, j), cf_j = room_lane(cf, j);
+        const int fl_j = __builtin_amdgcn_readlane(fl, j);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+#pragma clang fp contract(off)
+          const int k = lane - kRirHalf + 64 * t;
+          const double x = (double)k - f_j;
+          const int n = fl_j + k;
+          if (k <= kRirHalf && n >= 0 && n < L && fabs(x) <= 40.5) {
+            const double w = 0.5 * (1.0 + (ck[t] * cf_j + sk[t] * sf_j));
+            const double sinc = (x == 0.0) ? 1.0 : sgn * sp_j / (M_PI * x);
+            room_h[n] += a_j * w * sinc;
+          }
+          room_wave_lds_sync();
+        }
+      }
+    }
+  }
+  double* o = O.p + (long long)(bs / n_src) * O.sb + (long long)(bs % n_src) * O.ss +
+              (long long)mic * O.sm;
+  for (int i = lane; i < L; i += 64) o[(long long)i * O.si] = room_h[i];
+}
+
+// Sources packed two per complex signal and zero padded to the convolution length Lc.
+__global__ void __launch_bounds__(256) room_pack_kernel(SceneArgs A, double2* z, long long sb,
+                                                        int Lc) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= Lc) return;
+  const int b = blockIdx.y, p = blockIdx.z;
+  const float* y = A.src + (long long)b * A.n_src * A.n;
+  double re = 0.0, im = 0.0;
+  if (m < A.n) {
+    re = (double)y[(long long)(2 * p) * A.n + m];
+    if (2 * p + 1 < A.n_src) im = (double)y[(long long)(2 * p + 1) * A.n + m];
+  }
+  z[(long long)b * sb + (long long)p * Lc + m] = make_double2(re, im);
+}
+
+// Zero padding of the packed RIR signals h0 + i h1 (signals P .. P + n_src - 1).
+__global__ void __launch_bounds__(256) room_pad_kernel(double2* z, long long sb, int P, int rir_len,
+                                                       int Lc) {
+  const int m = rir_len + blockIdx.x * 256 + threadIdx.x;
+  if (m >= Lc) return;
+  z[(long long)blockIdx.y * sb + (long long)(P + blockIdx.z) * Lc + m] = make_double2(0.0, 0.0);
+}
+
+// Thread per bin k < Lc of utterance b: the real source's spectrum Y_s (from the packed
+// transform) times the spectrum of h0 + i h1 is the spectrum of image0 + i image1; summed
+// over the target and over the interferers: zo[b][0] = T0 + i T1, zo[b][1] = I0 + i I1.
+__global__ void __launch_bounds__(256) room_product_kernel(const double2* zf, double2* zo,
+                                                           int n_src, int Lc, long long sb) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= Lc) return;
+  const int b = blockIdx.y;
+  const int kp = (Lc - k) % Lc;
+  const int P = (n_src + 1) / 2;
+  const double2* zb = zf + (long long)b * sb;
+  double2 T = {0, 0}, I = {0, 0};
+  for (int s = 0; s < n_src; ++s) {
+    const double2* zp = zb + (long long)(s >> 1) * Lc;
+    const double2 z = zp[k], zc = zp[kp];
+    double2 Y;
+    if ((s & 1) == 0)
+      Y = make_double2(0.5 * (z.x + zc.x), 0.5 * (z.y - zc.y));  // (Z + conj Zc) / 2
+    else
+      Y = make_double2(0.5 * (z.y + zc.y), 0.5 * (zc.x - z.x));  // (Z - conj Zc) / 2i
+    const double2 H = zb[(long long)(P + s) * Lc + k];
+    double2& acc = (s == 0) ? T : I;
+    acc.x += Y.x * H.x - Y.y * H.y;
+    acc.y += Y.x * H.y + Y.y * H.x;
+  }
+  double2* o = zo + (long long)b * sb;
+  o[k] = T;
+  o[(long long)Lc + k] = I;
+}
+
+// Source positions of the reverberant generator: the target, interferer 1, and interferers
+// 2.. at (1 + u0 (dim_x - 2), 1 + u1 (dim_y - 2), target z) (simulation.py:133-136).
+struct RoomPos {
+  double t[3], i[3];
+};
+__global__ void __launch_bounds__(64) room_pos_kernel(GenArgs G, RoomArgs R, RoomPos Q, double* pos) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= G.batch * G.n_src) return;
+  const int b = t / G.n_src, s = t % G.n_src;
+  double* p = pos + (long long)t * 3;
+  if (s < 2) {
+    for (int a = 0; a < 3; ++a) p[a] = s ? Q.i[a] : Q.t[a];
+    return;
+  }
+  uint32_t k0, k1;
+  gen_key(G, b, k0, k1);
+  const uint32_t j = kUnifPos + 2u * (uint32_t)(s - 2);
+  p[0] = 1.0 + uniform(k0, k1, j) * (R.dim[0] - 2.0);
+  p[1] = 1.0 + uniform(k0, k1, j + 1u) * (R.dim[1] - 2.0);
+  p[2] = Q.t[2];
+}
+
 }  // namespace avz
 
 using namespace avz;
@@ -596,7 +785,7 @@ extern "C" int avz_launch_scene(const SceneArgs* a, void* ws, void* stream) {
                        (const double2*)f, o, sb);
     double2* t = fft_run(o, f, n, B, 2, sb, 1.0, st);
     hipLaunchKernelGGL(avz_scene_mix_kernel, dim3(B), dim3(kMixThreads), 0, st, *a,
-                       (const double2*)t, sb);
+                       (const double2*)t, sb, n);
   } else {
     SceneArgs c = *a;
     const long long per = (long long)B * a->n_src * 2 * n;
@@ -611,7 +800,7 @@ extern "C" int avz_launch_scene(const SceneArgs* a, void* ws, void* stream) {
     hipLaunchKernelGGL(scene_conv_pack_kernel, dim3((n + 255) / 256, B), dim3(256), 0, st, c, zo,
                        2LL * n);
     hipLaunchKernelGGL(avz_scene_mix_kernel, dim3(B), dim3(kMixThreads), 0, st, c,
-                       (const double2*)zo, 2LL * n);
+                       (const double2*)zo, 2LL * n, n);
   }
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -629,13 +818,14 @@ extern "C" long long avz_scene_gen_ws(int batch, int n_src, int n) {
   return gen_scratch(batch, n_src, n) + avz_scene_mix_ws(batch, n_src, n);
 }
 
-extern "C" int avz_launch_scene_generate(SceneArgs* a, long long start, uint32_t seed, void* ws,
-                                         void* stream) {
-  hipStream_t st = (hipStream_t)stream;
+// Front end of both generators: the sources and the noise of utterances start .. start +
+// B - 1 (and the anechoic azimuths) into the scratch at ws; returns the first byte after it.
+static char* gen_front(SceneArgs* a, long long start, uint32_t seed, void* ws, hipStream_t st,
+                       GenArgs& g) {
   const int B = a->batch, S = a->n_src, n = a->n;
   auto al = [](long long x) { return (x + 255) & ~255LL; };
   char* p = static_cast<char*>(ws);
-  GenArgs g{};
+  g = GenArgs{};
   g.batch = B;
   g.n_src = S;
   g.n = n;
@@ -657,11 +847,116 @@ extern "C" int avz_launch_scene_generate(SceneArgs* a, long long start, uint32_t
   hipLaunchKernelGGL(scene_ar_kernel<false>, dim3((unsigned)((nar + 255) / 256)), dim3(256), 0, st, g);
   hipLaunchKernelGGL(scene_ar_scan_kernel, dim3((B * S + 63) / 64), dim3(64), 0, st, g);
   hipLaunchKernelGGL(scene_ar_kernel<true>, dim3((unsigned)((nar + 255) / 256)), dim3(256), 0, st, g);
-  const long long nn = (long long)B * n;  // B * 2 * (n / 2) normal pairs
+  const long long nn = (long long)B * 2 * ((n + 1) / 2);  // normal pairs
   hipLaunchKernelGGL(scene_noise_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, g);
   a->src = g.src;
   a->noise = g.noise;
   a->angles_deg = g.angles;
+  return p;
+}
+
+extern "C" int avz_launch_scene_generate(SceneArgs* a, long long start, uint32_t seed, void* ws,
+                                         void* stream) {
+  GenArgs g;
+  char* p = gen_front(a, start, seed, ws, (hipStream_t)stream, g);
   if (hipGetLastError() != hipSuccess) return -3;
   return avz_launch_scene(a, p, stream);
+}
+
+// ================================================================ shoebox rooms: host side
+extern "C" long long avz_room_rir_samples(const double* dim, int max_order, double fs,
+                                          double c_sound) {
+  double dmax = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    double q = (max_order + 1) * dim[a];
+    q *= q;
+    for (int o = 0; o < 3; ++o)
+      if (o != a) q += dim[o] * dim[o];
+    dmax = std::max(dmax, std::sqrt(q));
+  }
+  const double v = std::floor(fs / c_sound * dmax) + 42.0;
+  return v < 1e15 ? (long long)v : (long long)1e15;
+}
+
+extern "C" int avz_room_conv_len(int n, int rir_len) {
+  int rad[32];
+  int m = n + rir_len - 1;
+  while (fft_factor(m, rad) == 0) ++m;
+  return m;
+}
+
+static void room_rir_launch(const RoomArgs* r, int batch, int n_src, const double* src_pos,
+                            const RirOut& o, hipStream_t st) {
+  hipLaunchKernelGGL(avz_room_rir_kernel, dim3((unsigned)(2LL * batch * n_src)), dim3(64),
+                     (size_t)r->rir_len * sizeof(double), st, *r, n_src, src_pos, o);
+}
+
+extern "C" int avz_launch_room_rir(const RoomArgs* r, int batch, int n_src, const double* src_pos,
+                                   double* rir, void* stream) {
+  const long long L = r->rir_len;
+  room_rir_launch(r, batch, n_src, src_pos, RirOut{rir, 2 * L * n_src, 2 * L, (int)L, 1},
+                  (hipStream_t)stream);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// Workspace of the reverberant back end: 2 x [B][ceil(n_src/2) + n_src][Lc] double2 (the
+// packed sources and the packed RIRs, ping-pong).
+extern "C" long long avz_scene_reverb_ws(const RoomArgs* r, int batch, int n_src, int n) {
+  const long long nz = (n_src + 1) / 2 + n_src;
+  return 2LL * batch * nz * avz_room_conv_len(n, r->rir_len) * (long long)sizeof(double2);
+}
+
+extern "C" int avz_launch_scene_reverb(const RoomArgs* r, const SceneArgs* a, void* ws,
+                                       void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int B = a->batch, S = a->n_src, n = a->n, P = (S + 1) / 2, L = r->rir_len;
+  const int Lc = avz_room_conv_len(n, L);
+  const long long sb = (long long)(P + S) * Lc;
+  double2* z0 = static_cast<double2*>(ws);
+  double2* z1 = z0 + (long long)B * sb;
+  hipLaunchKernelGGL(room_pack_kernel, dim3((Lc + 255) / 256, B, P), dim3(256), 0, st, *a, z0, sb, Lc);
+  // RIRs straight into the packed layout: mic 0 the real part, mic 1 the imaginary part
+  room_rir_launch(r, B, S, a->angles_deg,
+                  RirOut{reinterpret_cast<double*>(z0 + (long long)P * Lc), 2 * sb, 2LL * Lc, 1, 2}, st);
+  if (Lc > L)
+    hipLaunchKernelGGL(room_pad_kernel, dim3((Lc - L + 255) / 256, B, S), dim3(256), 0, st, z0, sb,
+                       P, L, Lc);
+  double2* f = fft_run(z0, z1, Lc, B, P + S, sb, -1.0, st);
+  double2* o = (f == z0) ? z1 : z0;
+  hipLaunchKernelGGL(room_product_kernel, dim3((Lc + 255) / 256, B), dim3(256), 0, st,
+                     (const double2*)f, o, S, Lc, sb);
+  double2* t = fft_run(o, f, Lc, B, 2, sb, 1.0, st);
+  hipLaunchKernelGGL(avz_scene_mix_kernel, dim3(B), dim3(kMixThreads), 0, st, *a,
+                     (const double2*)t, sb, Lc);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+static long long room_pos_bytes(int batch, int n_src) {
+  return ((long long)batch * n_src * 3 * 8 + 255) & ~255LL;
+}
+
+extern "C" long long avz_scene_reverb_gen_ws(const RoomArgs* r, int batch, int n_src, int n) {
+  return gen_scratch(batch, n_src, n) + room_pos_bytes(batch, n_src) +
+         avz_scene_reverb_ws(r, batch, n_src, n);
+}
+
+extern "C" int avz_launch_scene_reverb_generate(const RoomArgs* r, SceneArgs* a, long long start,
+                                                uint32_t seed, const double* target_pos,
+                                                const double* interferer_pos, void* ws,
+                                                void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  GenArgs g;
+  char* p = gen_front(a, start, seed, ws, st, g);
+  double* pos = reinterpret_cast<double*>(p);
+  p += room_pos_bytes(a->batch, a->n_src);
+  RoomPos q;
+  for (int i = 0; i < 3; ++i) {
+    q.t[i] = target_pos[i];
+    q.i[i] = interferer_pos[i];
+  }
+  hipLaunchKernelGGL(room_pos_kernel, dim3((a->batch * a->n_src + 63) / 64), dim3(64), 0, st, g, *r,
+                     q, pos);
+  a->angles_deg = pos;
+  if (hipGetLastError() != hipSuccess) return -3;
+  return avz_launch_scene_reverb(r, a, p, stream);
 }
