@@ -358,6 +358,44 @@ int avz_projection_metrics_scaled(int batch, int max_len, const int* len, const 
                                   long long itf_stride, double* sums, double* metrics,
                                   void* hip_stream);
 
+/* Short-time objective intelligibility of a batch: the stoi(s_tgt, s_est, config.FS,
+ * extended=False) score of Final_pipeline/src/metrics.py:157-160, as the published algorithm
+ * (Taal, Hendriks, Heusdens, Jensen 2011; avz/stoi.py stoi_numpy is the
+ * fp64 restatement), not pystoi's bits. Per pair (clean x, processed y, len[b] samples each):
+ * 16 kHz -> 10 kHz by the 581-tap 5/8 polyphase Kaiser filter (fp64 sums, fp32 storage;
+ * 10 kHz passes through); frames of 256 at hop 128 starting at 0, 128, ... < n10 - 256 under
+ * hanning(258)[1:-1]; the frames whose clean energy is within 40 dB of the loudest are kept
+ * (K of them) and overlap-added; the J = K - 1 frames of the joined signals are windowed
+ * again and transformed (512 points, fp32); 15 third-octave bands from 150 Hz (fp64 sums);
+ * d = the mean over the J - 29 segments of 30 frames and the bands of the correlation of the
+ * mean-removed x with the scaled, clipped (-15 dB) and mean-removed y (fp64).
+ * info[b] = { status, frames, K, segments }: status 0; 1 = fewer than 30 joined frames (or
+ * none at all), stoi[b] = 1e-5; 2 = a clean frame energy is not finite, stoi[b] = NaN. A NaN
+ * in y alone gives status 0 and stoi[b] = NaN. An utterance's values never reach another's.
+ * Repeated calls give identical bits. stoi does not depend on the scale of y.
+ * fs: 16000 or 10000 (else AVZ_ERR_UNSUPPORTED). len[b] is clamped to [0, max_len].
+ * batch <= 32767, max_len < 2^30, strides (elements) >= max_len, res_stride >= the 10-kHz
+ * length of max_len (ceil(5 max_len / 8) at 16 kHz), tob_stride >= its frame count - 1,
+ * workspace_bytes >= avz_stoi_workspace_bytes() (else AVZ_ERR_SHAPE); workspace 256-byte
+ * aligned. The stage exports hold the 10-kHz signals (x then y) and the band values of the
+ * first K - 1 frames. No plan, no allocation on the call. Device arrays. */
+typedef struct avz_stoi_args {
+  int batch, max_len;
+  const int* len;            /* device [batch], or NULL = max_len                      */
+  double fs;                 /* 16000 or 10000, else AVZ_ERR_UNSUPPORTED               */
+  const float* clean; long long clean_stride;
+  const float* est;   long long est_stride;
+  double* stoi;              /* device [batch]                                          */
+  int* info;                 /* optional device [batch][4]: status, frames, kept K, segments */
+  float* resampled;          /* optional debug: [batch][2][res_stride] 10-kHz signals   */
+  long long res_stride;
+  double* tob;               /* optional debug: [batch][2][15][tob_stride] band values  */
+  long long tob_stride;
+  void* workspace; long long workspace_bytes;
+} avz_stoi_args;
+long long avz_stoi_workspace_bytes(int batch, int max_len, double fs);
+int avz_stoi_batch(const avz_stoi_args* args, void* hip_stream);
+
 /* Synthetic scene mixing on the device — the anechoic far-field generator of
  * full_audio_generating_pipeline/world_building.py:47-59 (per-mic fractional delay by an
  * rfft phase shift over the whole signal, d = mic_d, c = c_sound) with the SIR gain

@@ -45,6 +45,7 @@ EXPORTED = [
     "avz_room_rir_len", "avz_room_rir", "avz_scene_reverb_workspace_bytes",
     "avz_scene_reverb_mix", "avz_scene_reverb_generate_workspace_bytes",
     "avz_scene_reverb_generate",
+    "avz_stoi_workspace_bytes", "avz_stoi_batch",
 ]
 
 
@@ -98,6 +99,18 @@ class AvzWpeArgs(ct.Structure):
         ("Z", ct.c_void_p), ("z_stride_b", ct.c_longlong), ("z_stride_m", ct.c_longlong),
         ("z_stride_f", ct.c_longlong),
         ("status", ct.c_void_p),
+    ]
+
+
+class AvzStoiArgs(ct.Structure):
+    _fields_ = [
+        ("batch", ct.c_int), ("max_len", ct.c_int), ("len", ct.c_void_p), ("fs", ct.c_double),
+        ("clean", ct.c_void_p), ("clean_stride", ct.c_longlong),
+        ("est", ct.c_void_p), ("est_stride", ct.c_longlong),
+        ("stoi", ct.c_void_p), ("info", ct.c_void_p),
+        ("resampled", ct.c_void_p), ("res_stride", ct.c_longlong),
+        ("tob", ct.c_void_p), ("tob_stride", ct.c_longlong),
+        ("workspace", ct.c_void_p), ("workspace_bytes", ct.c_longlong),
     ]
 
 
@@ -191,6 +204,12 @@ def _load():
     for name in ("avz_room_rir_len", "avz_room_rir", "avz_scene_reverb_mix",
                  "avz_scene_reverb_generate"):
         getattr(lib, name).restype = ct.c_int
+    lib.avz_stoi_workspace_bytes.argtypes = [I, I, D]
+    lib.avz_stoi_workspace_bytes.restype = LL
+    lib.avz_stoi_batch.argtypes = [ct.POINTER(AvzStoiArgs), P]
+    lib.avz_stoi_batch.restype = ct.c_int
+    lib.avz_stoi_taps.argtypes = [DP]
+    lib.avz_stoi_taps.restype = ct.c_int
     lib.avz_strerror.argtypes = [ct.c_int]
     lib.avz_strerror.restype = ct.c_char_p
     lib.avz_last_hip_error.restype = ct.c_char_p

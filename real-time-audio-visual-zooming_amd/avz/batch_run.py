@@ -10,9 +10,10 @@ utterances, scores them on the device, and the only collective is an all-reduce 
 metric sums (RCCL over xGMI on GPUs, gloo in CPU tests; on a CPU device the scenes come
 from the generator's host restatement, synth.make_batch_philox, so they are the same).
 
-Rows follow batch_metrics.csv (Final_pipeline/src/metrics.py:16-44); STOI/PESQ are
-reported as 0.0, exactly what the reference writes when pystoi/pesq are missing
-(metrics.py:8-14, 148-156).
+Rows follow batch_metrics.csv (Final_pipeline/src/metrics.py:16-44). By default STOI/PESQ
+are reported as 0.0, exactly what the reference writes when pystoi/pesq are missing
+(metrics.py:8-14, 148-156); ``run_batch(..., stoi=True)`` scores STOI on the device
+(avz.stoi) and fills the column. PESQ stays 0.0.
 """
 from __future__ import annotations
 
@@ -76,6 +77,10 @@ class BatchResult:
     # global [sum OSIR_in, sum OSIR_out, sum OSINR_in, sum OSINR_out, n_ok, n]; the sums
     # run over the n_ok utterances whose four metrics are finite
     sums: np.ndarray
+    # run_batch(..., stoi=True): global [sum STOI_in, sum STOI_out, n_ok] over the
+    # utterances whose two scores are finite (mixture channel 0 and the output against the
+    # target reference); None otherwise
+    stoi_sums: np.ndarray | None = None
 
     @property
     def mean_sir_improvement(self):
@@ -108,12 +113,16 @@ def run_batch(n_runs: int, start_idx: int = 0, n_interferers: int = 2, *,
               seconds: float = 4.0, batch: int = 256, device=None,
               enhance: Callable | None = None, csv_path: str | None = None,
               scenes: str = "philox", reverb: bool = False,
-              max_order: int = 15) -> BatchResult:
+              max_order: int = 15, stoi: bool = False) -> BatchResult:
     """batch_run.run_batch equivalent over a device batch, sharded over the group.
     scenes: "philox" (device generator; host restatement on CPU) or "host" (make_batch).
     reverb: the scenes of generate_scene(reverb=True) (simulation.py:105-165): the
     reference shoebox room with image sources up to max_order (synth.Room,
-    make_reverb_batch_device; on CPU the host restatement) in place of the anechoic model."""
+    make_reverb_batch_device; on CPU the host restatement) in place of the anechoic model.
+    stoi: also score STOI of mixture channel 0 and of the output against the target reference
+    (avz.stoi.stoi_batch, on the device; an un-normalised deferred output is scored as it is,
+    STOI does not depend on its scale), fill the rows' STOI column with the output's score and
+    return BatchResult.stoi_sums; the sums travel in the same all-reduce as ``sums``."""
     rank, world = world_info()
     lo, hi = shard(n_runs, rank, world)
     dev = torch.device(device) if device is not None else (
@@ -124,6 +133,7 @@ def run_batch(n_runs: int, start_idx: int = 0, n_interferers: int = 2, *,
         enhance = gpu_enhancer(max_batch=batch, max_samples=S, device=dev)
     rows = []
     sums = torch.zeros(6, dtype=torch.float64, device=dev)
+    stoi_sums = torch.zeros(3, dtype=torch.float64, device=dev) if stoi else None
     for c0 in range(start_idx + lo, start_idx + hi, batch):
         nb = min(batch, start_idx + hi - c0)
         if reverb and dev.type == "cuda":
@@ -158,15 +168,28 @@ def run_batch(n_runs: int, start_idx: int = 0, n_interferers: int = 2, *,
                                                       peak=peak)
         sums += finite_sums([osir_b, osir_s, osinr_b, osinr_s], nb)
         vals = torch.stack([osir_b, osir_s, osinr_b, osinr_s]).cpu().numpy()
+        stoi_col = ["0.0000"] * nb
+        if stoi:
+            from .stoi import stoi_batch
+            d_in, _ = stoi_batch(d_tgt[:, :L], d_mix[:, 0, :L], fs=synth.FS)
+            d_out, _ = stoi_batch(d_tgt[:, :L], out[:, :L], fs=synth.FS)
+            stoi_sums += finite_sums([d_in, d_out]).to(dev)
+            stoi_col = [f"{v:.4f}" for v in d_out.cpu().numpy()]
         for j in range(nb):
             rows.append({"Run_ID": f"batch_test_{c0 + j:03d}", "SIR_Base": f"{vals[0, j]:.2f}",
                          "SIR_Enh": f"{vals[1, j]:.2f}", "SIR_Imp": f"{vals[1, j] - vals[0, j]:.2f}",
                          "SINR_Base": f"{vals[2, j]:.2f}", "SINR_Enh": f"{vals[3, j]:.2f}",
-                         "STOI": "0.0000", "PESQ_WB": "0.0000", "PESQ_NB": "0.0000"})
-    allreduce_job(sums)  # the only collective: metric sums (+ n_ok, n)
+                         "STOI": stoi_col[j], "PESQ_WB": "0.0000", "PESQ_NB": "0.0000"})
+    if stoi:  # one collective still: [sums, stoi_sums] reduced together, then split
+        both = torch.cat([sums, stoi_sums])
+        allreduce_job(both)
+        sums, stoi_sums = both[:6], both[6:]
+    else:
+        allreduce_job(sums)  # the only collective: metric sums (+ n_ok, n)
     if csv_path is not None:
         append_csv(csv_path, rows, rank, world)
-    return BatchResult(rows=rows, sums=sums.cpu().numpy())
+    return BatchResult(rows=rows, sums=sums.cpu().numpy(),
+                       stoi_sums=stoi_sums.cpu().numpy() if stoi else None)
 
 
 def append_csv(path: str, rows: list, rank: int = 0, world: int = 1) -> None:

@@ -12,8 +12,9 @@ products per utterance in one streaming pass, then the reference's formulas). Ho
 tensors (CPU-only tooling and the gloo tests) use the same formulas in torch fp64.
 
 ``evaluate_run`` mirrors metrics.py:125-214: report.txt (same lines) and the
-batch_metrics.csv row; STOI/PESQ are 0.0 exactly as the reference writes them when
-pystoi/pesq are missing (metrics.py:8-14), which is the case in this image.
+batch_metrics.csv row; by default STOI/PESQ are 0.0 exactly as the reference writes them
+when pystoi/pesq are missing (metrics.py:8-14). ``evaluate_run(..., stoi=True)`` fills STOI
+from avz.stoi.stoi_batch (metrics.py:157-160); PESQ stays 0.0.
 """
 from __future__ import annotations
 
@@ -182,10 +183,11 @@ def append_to_csv(csv_path, rows):
 
 
 def evaluate_run(run_name, sim_dir_root=os.path.join("data", "simulated"),
-                 results_dir=os.path.join("data", "results"), device=None):
+                 results_dir=os.path.join("data", "results"), device=None, stoi=False):
     """metrics.py:125-214 on the device: OSIR/OSINR of the mixture (baseline) and of the
     enhanced output in one avz_projection_metrics call; writes report.txt and appends
-    the batch_metrics.csv row. Returns the metrics dict."""
+    the batch_metrics.csv row. Returns the metrics dict. stoi: also score
+    stoi(s_tgt, s_est, 16000) on the device (avz.stoi.stoi_batch) instead of writing 0.0."""
     sim_dir = os.path.join(sim_dir_root, run_name)
     res_dir = os.path.join(results_dir, f"{run_name}_results")
     est_path = os.path.join(res_dir, f"{run_name}_enhanced.wav")
@@ -204,6 +206,9 @@ def evaluate_run(run_name, sim_dir_root=os.path.join("data", "simulated"),
     mm = projection_metrics(est, tg, it).cpu().numpy()
     m = dict(sir_b=float(mm[0, 1]), sinr_b=float(mm[0, 0]), sir_s=float(mm[1, 1]),
              sinr_s=float(mm[1, 0]), stoi=0.0, pesq_wb=0.0, pesq_nb=0.0)
+    if stoi:
+        from .stoi import stoi_batch
+        m["stoi"] = float(stoi_batch(tg[:1], est[1:2], fs=16000)[0][0])
     report = format_report(run_name, m)
     print(report)
     with open(os.path.join(res_dir, "report.txt"), "w") as fh:

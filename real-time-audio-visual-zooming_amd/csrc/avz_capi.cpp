@@ -647,6 +647,100 @@ extern "C" int avz_wpe_spectral(const avz_wpe_args* a, void* stream) {
   return hip_rc(avz_launch_wpe(&w, stream));
 }
 
+// STOI: sizes of a max_len utterance and the workspace carve (res, energy, kept, info, tob;
+// each piece 256-byte aligned). The workspace holds every piece whether or not the call
+// passes its own info / resampled / tob arrays.
+struct StoiShape {
+  int resample;
+  long long n10, nf, jmax;
+  size_t sz_res, sz_e, sz_k, sz_i, sz_t;
+  size_t bytes() const { return sz_res + sz_e + sz_k + sz_i + sz_t; }
+};
+
+static int stoi_shape(int batch, int max_len, double fs, StoiShape* s) {
+  if (fs != 16000.0 && fs != 10000.0) return AVZ_ERR_UNSUPPORTED;
+  // 2 batch rows of blocks in the resampler's grid; 8 m + 290 stays far inside 64 bits
+  if (batch < 0 || batch > 32767 || max_len < 0 || max_len > 0x3fffffff) return AVZ_ERR_SHAPE;
+  s->resample = fs == 16000.0;
+  s->n10 = s->resample ? (5LL * max_len + 7) / 8 : max_len;
+  s->nf = s->n10 > 256 ? (s->n10 - 256 + 127) / 128 : 0;
+  s->jmax = s->nf > 1 ? s->nf - 1 : 0;
+  const size_t B = (size_t)batch;
+  s->sz_res = s->resample ? align256(sizeof(float) * 2 * B * (size_t)s->n10) : 0;
+  s->sz_e = align256(sizeof(double) * B * (size_t)s->nf);
+  s->sz_k = align256(sizeof(int) * B * (size_t)s->nf);
+  s->sz_i = align256(sizeof(int) * 4 * B);
+  s->sz_t = align256(sizeof(double) * 2 * 15 * B * (size_t)s->jmax);
+  return AVZ_OK;
+}
+
+extern "C" long long avz_stoi_workspace_bytes(int batch, int max_len, double fs) {
+  StoiShape s;
+  const int e = stoi_shape(batch, max_len, fs, &s);
+  return e != AVZ_OK ? e : (long long)s.bytes();
+}
+
+extern "C" int avz_stoi_batch(const avz_stoi_args* a, void* stream) {
+  if (!a) return AVZ_ERR_ARG;
+  StoiShape s;
+  const int e = stoi_shape(a->batch, a->max_len, a->fs, &s);
+  if (e != AVZ_OK) return e;
+  if (a->batch == 0) return AVZ_OK;
+  if (!a->clean || !a->est || !a->stoi || !a->workspace) return AVZ_ERR_ARG;
+  if (misaligned(a->clean, 4) || misaligned(a->est, 4) || misaligned(a->len, 4) ||
+      misaligned(a->stoi, 8) || misaligned(a->info, 4) || misaligned(a->resampled, 4) ||
+      misaligned(a->tob, 8) || misaligned(a->workspace, 256))
+    return AVZ_ERR_ALIGN;
+  if (a->workspace_bytes < (long long)s.bytes()) return AVZ_ERR_SHAPE;
+  if (a->batch > 1 && (a->clean_stride < a->max_len || a->est_stride < a->max_len))
+    return AVZ_ERR_SHAPE;
+  if (a->resampled && a->res_stride < s.n10) return AVZ_ERR_SHAPE;
+  if (a->tob && a->tob_stride < s.jmax) return AVZ_ERR_SHAPE;
+
+  char* q = static_cast<char*>(a->workspace);
+  float* ws_res = reinterpret_cast<float*>(q); q += s.sz_res;
+  double* ws_e = reinterpret_cast<double*>(q); q += s.sz_e;
+  int* ws_k = reinterpret_cast<int*>(q); q += s.sz_k;
+  int* ws_i = reinterpret_cast<int*>(q); q += s.sz_i;
+  double* ws_t = reinterpret_cast<double*>(q);
+
+  avz::StoiArgs k{};
+  k.batch = a->batch;
+  k.max_len = a->max_len;
+  k.len = a->len;
+  k.resample = s.resample;
+  k.n10_max = (int)s.n10;
+  k.nf_max = (int)s.nf;
+  k.clean = a->clean;
+  k.est = a->est;
+  k.clean_stride = a->clean_stride;
+  k.est_stride = a->est_stride;
+  if (a->resampled) {
+    k.res = a->resampled;
+    k.res_stride = a->res_stride;
+  } else if (s.resample) {
+    k.res = ws_res;
+    k.res_stride = s.n10;
+  }
+  if (s.resample) {
+    k.x10 = k.res;
+    k.y10 = k.res + k.res_stride;
+    k.x10_stride = k.y10_stride = 2 * k.res_stride;
+  } else {
+    k.x10 = a->clean;
+    k.y10 = a->est;
+    k.x10_stride = a->clean_stride;
+    k.y10_stride = a->est_stride;
+  }
+  k.energy = ws_e;
+  k.kept = ws_k;
+  k.info = a->info ? a->info : ws_i;
+  k.tob = a->tob ? a->tob : ws_t;
+  k.tob_stride = a->tob ? a->tob_stride : s.jmax;
+  k.stoi = a->stoi;
+  return hip_rc(avz_launch_stoi(&k, stream));
+}
+
 extern "C" int avz_solve_covariance(const avz_plan* p, int batch, const double* cov, float* w,
                                     const double* steer, int* fallback, void* stream) {
   if (!p) return AVZ_ERR_ARG;

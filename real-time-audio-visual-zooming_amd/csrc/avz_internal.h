@@ -195,6 +195,28 @@ struct WpeArgs {
   int* status;                // [B][bins] or null
 };
 
+// Batched STOI (avz_stoi_batch, avz_stoi.hip).
+struct StoiArgs {
+  int batch, max_len;
+  const int* len;             // [B] samples (clamped to [0, max_len]) or null = max_len
+  int resample;               // 1: 16-kHz input through the 5/8 resampler; 0: 10-kHz input
+  int n10_max, nf_max;        // 10-kHz samples / frames of a max_len utterance
+  const float* clean;         // [B][clean_stride]
+  const float* est;           // [B][est_stride]
+  long long clean_stride, est_stride;
+  float* res;                 // [B][2][res_stride] 10-kHz signals, or null (resample == 0
+  long long res_stride;       // and no export: the resample kernel is not launched)
+  const float* x10;           // the 10-kHz clean / processed rows the later kernels read
+  const float* y10;
+  long long x10_stride, y10_stride;
+  double* energy;             // [B][nf_max] frame energies, dB
+  int* kept;                  // [B][nf_max] kept-frame list
+  int* info;                  // [B][4] status, frames, kept K, segments
+  double* tob;                // [B][2][15][tob_stride] band values
+  long long tob_stride;
+  double* stoi;               // [B]
+};
+
 struct StftArgs {
   int batch, channels;        // channels 1 or 2
   const int* len;             // clamped to max_len in the kernel
@@ -318,6 +340,8 @@ int avz_launch_spectral(int n_fft, const avz::SpecArgs* s, const avz::ChainArgs*
 int avz_launch_solve_cov(int n_fft, const avz::SpecArgs* s, const avz::ChainArgs* p, void* stream);
 int avz_wpe_max_frames(void);
 int avz_launch_wpe(const avz::WpeArgs* a, void* stream);
+int avz_launch_stoi(const avz::StoiArgs* a, void* stream);
+int avz_stoi_taps(double* out /*[291]*/);  // h'[290 + t], t = 0 .. 290, of the 16 -> 10 kHz resampler
 int avz_launch_srp(int n_fft, const avz::ChainArgs* a, const avz::SrpArgs* s, void* stream);
 int avz_chunk_frames(void);
 int avz_launch_stft(int n_fft, const avz::StftArgs* a, void* stream);
