@@ -329,6 +329,29 @@ int avz_mask_features(const avz_plan* plan, int layout, int batch, const int* le
                       long long s_b, long long s_c, long long s_f, long long s_t,
                       void* hip_stream);
 
+/* One training batch of the mask estimator, the sample of
+ * full_audio_generating_pipeline/model_training.py:80-92 (SpatialDataset.__getitem__) for
+ * `batch` items in one kernel (device arrays; no plan workspace, no allocation):
+ *  feat:  exactly what avz_mask_features writes for `layout` from `mix` (the same bits);
+ *  label[b*l_b + k*l_f + t*l_t] = 1.0f where |S_t[k,t]| > |S_i[k,t]|, else 0.0f, S_t / S_i
+ *    the STFTs (as above) of tgt[b] / itf[b] (at ref_stride floats per item).
+ * The label is decided on the kernel's own fp32 transforms, as the chain's ibm_kappa < 0 tier
+ * decides its mask: it is not the reference-exact decision of the IBM plans, so a (bin,
+ * frame) whose two magnitudes agree to within the fp32 transform's error may differ from
+ * numpy's np.where. Where both reference frames are all zeros the label is 0, exactly.
+ * Scaling tgt and itf by one power of two leaves every label unchanged.
+ * Frames t >= ceil(len[b]/hop) + 1 and items with len[b] < n_fft are not written (as
+ * avz_stft). The plan's mask mode is irrelevant. AVZ_ERR_ARG: a NULL pointer or an unknown
+ * layout; AVZ_ERR_SHAPE: batch > the plan's max_batch, max_len outside [n_fft,
+ * max_samples], ch_stride < max_len, or (batch > 1) mix_stride < ch_stride + max_len or
+ * ref_stride < max_len. */
+int avz_mask_training_batch(const avz_plan* plan, int layout, int batch, const int* len,
+                            int max_len, const float* mix, long long mix_stride,
+                            long long ch_stride, const float* tgt, const float* itf,
+                            long long ref_stride, float* feat, long long s_b, long long s_c,
+                            long long s_f, long long s_t, float* label, long long l_b,
+                            long long l_f, long long l_t, void* hip_stream);
+
 /* Steered response power scan, scripts/debug_srp.py:46-62 for a batch: for the
  * angles np.linspace(angle_lo, angle_hi, n_angles) (degrees, the plan's mic_d and
  * c_sound, debug_srp.py:17-23 geometry), P = sum over bins f_lo <= f <= f_hi and all

@@ -46,6 +46,7 @@ EXPORTED = [
     "avz_scene_reverb_mix", "avz_scene_reverb_generate_workspace_bytes",
     "avz_scene_reverb_generate",
     "avz_stoi_workspace_bytes", "avz_stoi_batch",
+    "avz_mask_training_batch",
 ]
 
 
@@ -208,6 +209,9 @@ def _load():
     lib.avz_stoi_workspace_bytes.restype = LL
     lib.avz_stoi_batch.argtypes = [ct.POINTER(AvzStoiArgs), P]
     lib.avz_stoi_batch.restype = ct.c_int
+    lib.avz_mask_training_batch.argtypes = [P, I, I, P, I, P, LL, LL, P, P, LL, P, LL, LL, LL, LL,
+                                            P, LL, LL, LL, P]
+    lib.avz_mask_training_batch.restype = ct.c_int
     lib.avz_stoi_taps.argtypes = [DP]
     lib.avz_stoi_taps.restype = ct.c_int
     lib.avz_strerror.argtypes = [ct.c_int]

@@ -436,6 +436,51 @@ def mask_features(plan: MVDRPlan, x: torch.Tensor, layout: str = "unet", lengths
     return out
 
 
+def mask_training_batch(plan: MVDRPlan, mix: torch.Tensor, tgt: torch.Tensor, itf: torch.Tensor,
+                        layout: str = "unet", lengths=None, max_len=None, stream=None):
+    """One training batch of the mask estimator in one kernel (avz_mask_training_batch):
+    (feat, label) of a [B, 2, S] mic pair and its [B, S] target / interference references.
+    feat: the bits mask_features(plan, mix, layout) returns; label [B, F, T] float32, 1.0
+    where |STFT(tgt)| > |STFT(itf)| on the kernel's fp32 transforms, else 0.0
+    (full_audio_generating_pipeline/model_training.py:80-92). Frames past an item's length
+    stay 0."""
+    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or mix.stride(2) != 1 \
+            or not mix.is_cuda:
+        raise ValueError("mix must be float32 [B, 2, S] on the device")
+    B, _, S = mix.shape
+    for name, r in (("tgt", tgt), ("itf", itf)):
+        if r.dim() != 2 or tuple(r.shape) != (B, S) or r.dtype != torch.float32 \
+                or r.stride(1) != 1 or r.device != mix.device:
+            raise ValueError(f"{name} must be float32 [{B}, {S}] on the mixture's device")
+    if itf.stride(0) != tgt.stride(0):
+        itf = itf.contiguous()
+        tgt = tgt.contiguous()
+    if lengths is None:
+        lengths = torch.full((B,), S, dtype=torch.int32, device=mix.device)
+        max_len = S
+    if max_len is None:
+        max_len = int(lengths.max().item())
+    T = n_frames(max_len, plan.hop)
+    F = plan.F
+    if layout == "unet":
+        feat = torch.zeros((B, 2, F, T), dtype=torch.float32, device=mix.device)
+        sb, sc, sf, st = feat.stride()
+    elif layout == "tflite":
+        feat = torch.zeros((B, F, T, 4), dtype=torch.float32, device=mix.device)
+        sb, sf, st, sc = feat.stride()
+    else:
+        raise ValueError(f"unknown feature layout {layout!r}")
+    label = torch.zeros((B, F, T), dtype=torch.float32, device=mix.device)
+    check(lib.avz_mask_training_batch(
+        plan._h, FEATURE_LAYOUTS[layout], B, ct.c_void_p(lengths.data_ptr()), int(max_len),
+        ct.c_void_p(mix.data_ptr()), mix.stride(0), mix.stride(1),
+        ct.c_void_p(tgt.data_ptr()), ct.c_void_p(itf.data_ptr()), tgt.stride(0),
+        ct.c_void_p(feat.data_ptr()), sb, sc, sf, st,
+        ct.c_void_p(label.data_ptr()), label.stride(0), label.stride(1), label.stride(2),
+        _stream_handle(stream)), "avz_mask_training_batch")
+    return feat, label
+
+
 def srp_scan(plan: MVDRPlan, mix: torch.Tensor, lengths=None, max_len=None, n_angles=181,
              angle_lo=0.0, angle_hi=180.0, f_lo=200.0, f_hi=4000.0, stream=None):
     """scripts/debug_srp.py:46-62 for a [B, 2, S] batch -> power map [B, n_angles] in dB

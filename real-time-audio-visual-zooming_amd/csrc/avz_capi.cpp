@@ -931,6 +931,48 @@ extern "C" int avz_mask_features(const avz_plan* p, int layout, int batch, const
   return rc;
 }
 
+extern "C" int avz_mask_training_batch(const avz_plan* p, int layout, int batch, const int* len,
+                                       int max_len, const float* mix, long long mix_stride,
+                                       long long ch_stride, const float* tgt, const float* itf,
+                                       long long ref_stride, float* feat, long long s_b,
+                                       long long s_c, long long s_f, long long s_t, float* label,
+                                       long long l_b, long long l_f, long long l_t, void* stream) {
+  if (!p || !len || !mix || !tgt || !itf || !feat || !label) return AVZ_ERR_ARG;
+  if (layout != AVZ_FEAT_LOGMAG_IPD && layout != AVZ_FEAT_TFLITE) return AVZ_ERR_ARG;
+  const avz_config& c = p->cfg;
+  if (batch < 0 || batch > c.max_batch) return AVZ_ERR_SHAPE;
+  if (max_len < c.n_fft || max_len > c.max_samples) return AVZ_ERR_SHAPE;
+  if (batch == 0) return AVZ_OK;
+  if (ch_stride < max_len) return AVZ_ERR_SHAPE;
+  if (batch > 1 && (mix_stride < ch_stride + max_len || ref_stride < max_len))
+    return AVZ_ERR_SHAPE;
+  avz::TrainArgs t{};
+  t.s.batch = batch;
+  t.s.channels = 2;
+  t.s.len = len;
+  t.s.x = mix;
+  t.s.x_stride = mix_stride;
+  t.s.ch_stride = ch_stride;
+  t.s.max_frames = frames_for(max_len, c.hop);
+  t.s.max_len = max_len;
+  t.s.feat = layout;
+  t.s.F_out = feat;
+  t.s.f_sb = s_b;
+  t.s.f_sc = s_c;
+  t.s.f_sf = s_f;
+  t.s.f_st = s_t;
+  t.tgt = tgt;
+  t.itf = itf;
+  t.ref_stride = ref_stride;
+  t.label = label;
+  t.l_sb = l_b;
+  t.l_sf = l_f;
+  t.l_st = l_t;
+  const int rc = avz_launch_train(c.n_fft, &t, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
 extern "C" int avz_srp_scan(const avz_plan* p, int batch, const int* len, int max_len,
                             const float* mix, long long mix_stride, long long ch_stride,
                             int n_angles, double angle_lo, double angle_hi, double f_lo,

@@ -232,6 +232,17 @@ struct StftArgs {
 };
 enum : int { FEAT_NONE = 0, FEAT_LOGMAG_IPD = 1, FEAT_TFLITE = 2 };
 
+// Mask-estimator training batch (avz_mask_training_batch, avz_train.hip): the features of
+// `s` (x = the mic pair, feat != FEAT_NONE) and the IBM label of the two references.
+struct TrainArgs {
+  StftArgs s;
+  const float* tgt;           // [B][ref_stride] target reference
+  const float* itf;           // [B][ref_stride] interference reference
+  long long ref_stride;
+  float* label;               // label[b*l_sb + k*l_sf + t*l_st] = 1.0f or 0.0f
+  long long l_sb, l_sf, l_st;
+};
+
 struct SrpArgs {
   int n_angles;
   double angle_lo, angle_hi;  // np.linspace(angle_lo, angle_hi, n_angles)
@@ -345,4 +356,5 @@ int avz_stoi_taps(double* out /*[291]*/);  // h'[290 + t], t = 0 .. 290, of the 
 int avz_launch_srp(int n_fft, const avz::ChainArgs* a, const avz::SrpArgs* s, void* stream);
 int avz_chunk_frames(void);
 int avz_launch_stft(int n_fft, const avz::StftArgs* a, void* stream);
+int avz_launch_train(int n_fft, const avz::TrainArgs* a, void* stream);
 }
