@@ -507,6 +507,76 @@ int avz_scene_reverb_generate(const avz_room* room, int batch, long long start_i
                               float* itf, long long ref_stride, void* workspace,
                               long long workspace_bytes, void* hip_stream);
 
+/* ------------------------------------------------------------------ streaming causal MVDR
+ * The chain of avz_mvdr_batch run hop by hop with state carried between calls: the causal
+ * ("real-time") form of oracle_debug.enhance / process_chunk, which the reference leaves as
+ * its open latency item. The algorithm is the contract (avz/stream.py
+ * stream_numpy is the fp64 restatement). With H = n_fft / 2, x_t the t-th hop pushed since
+ * the last reset (both mics) and x_-1 = 0:
+ *  - frame t = [x_t-1 | x_t] under the plan's fp32 periodic Hann, scaled by 1 / sum(w): frame
+ *    t of scipy.signal.stft(x, nperseg=n_fft, noverlap=n_fft/2);
+ *  - noise weight n_t[k] of the plan's mask mode: AVZ_MASK_EXTERNAL 1 - M[k][t] (covariance
+ *    weight n_t + weight_eps, as the chain); AVZ_MASK_IBM 1 where |S_i| > |S_t| on the
+ *    kernel's own fp32 reference transforms (the ibm_kappa < 0 tier, as
+ *    avz_mask_training_batch; two all-zero reference frames give exactly 0); AVZ_MASK_ONES 1;
+ *  - sums, fp64, per bin: c_t = forget c_t-1 + n_t (|y0|^2, |y1|^2, Re y0 y1*, Im y0 y1*, 1)
+ *    where the stream's adapt flag is non-zero, else c_t = c_t-1 (covariance gating: the
+ *    weights freeze);
+ *  - weights w_t = the plan's MVDR solve of c_t (sigma, fmin_hz, singular_fallback MIC0 or
+ *    MEAN) with the STREAM's steering vector; S_t = w_t^H Y_t times the plan's post-filter
+ *    gain of frame t (NONE, IBM_TARGET 1 - n_t, EXT_FLOOR max(M, pf_floor), EXT_MUL M);
+ *  - g_t = irfft(S_t) sum(w) w; output hop t = (g_t-1[H:] + g_t[:H]) / (w^2[m] + w^2[m + H])
+ *    for t >= 1 and zeros for t = 0: scipy.signal.istft of the causal S delayed by one hop,
+ *    the algorithmic latency. One extra hop of zeros drains the last H samples.
+ * forget in (0, 1]; 1 gives running sums, which after the drain hop equal the offline sums.
+ * AVZ_ERR_UNSUPPORTED (before any device work): AVZ_BF_HYBRID_NULL, AVZ_MASK_IPD, AVZ_PF_IRM,
+ * AVZ_FALLBACK_BATCH, AVZ_NORM_PEAK (a peak is not causal).
+ *
+ * The state is one caller-owned device buffer of avz_stream_state_bytes(plan, streams) bytes,
+ * 256-byte aligned, for streams <= the plan's max_batch; its layout is private (per stream:
+ * a 64-bit frame count, the previous hop of the mics and references, the synthesis tail, the
+ * sums [F][5] and the steering table [F][4] in fp64; about 47 KB at n_fft = 1024). No call
+ * allocates.
+ *  avz_stream_reset  zeroes the selected streams (select[s] != 0; NULL = all) and copies the
+ *                    plan's steering table into them. A new buffer must be reset first.
+ *  avz_stream_steer  rewrites the table of every stream whose angle_deg[s] is not NaN, on
+ *                    the device: tau1 = (d/2) cos(theta) / c, tau2 = (d/2) cos(theta - pi) / c,
+ *                    d_m = exp(-2 pi i f_k tau_m) (masked_mvdr.py:22-35), in fp64. The new
+ *                    direction applies from the next pushed frame.
+ *  avz_stream_push   `hops` >= 1 new hops per stream; out gets the same number of samples.
+ * Checks, all on the host before any HIP call: a NULL plan, args, mix, out, state (or the
+ * mask mode's ref_tgt / ref_int / ext_mask, or angle_deg), hops < 1 or forget outside (0, 1]:
+ * AVZ_ERR_ARG; streams outside 1 .. max_batch, ch_stride or out_stride < hops * hop,
+ * (streams > 1) mix_stride < ch_stride + hops * hop or ref_stride < hops * hop, or
+ * state_bytes too small: AVZ_ERR_SHAPE; state not 256-byte aligned, out not 16-byte aligned
+ * or out_stride % 4 != 0: AVZ_ERR_ALIGN.
+ * Guarantees: a stream's outputs and final state are bit-identical however its hops are
+ * grouped into calls (1 x T, T x 1 or ragged), whatever its index in the buffer and whatever
+ * the other streams hold; a NaN in one stream never reaches another. Calls on one state
+ * buffer must be stream-ordered; calls on distinct state buffers may run concurrently. */
+long long avz_stream_state_bytes(const avz_plan* plan, int streams);
+int avz_stream_reset(const avz_plan* plan, void* state, long long state_bytes, int streams,
+                     const int* select /* device [streams] or NULL = all */, void* hip_stream);
+int avz_stream_steer(const avz_plan* plan, void* state, long long state_bytes, int streams,
+                     const double* angle_deg /* device [streams]; NaN = keep */,
+                     void* hip_stream);
+typedef struct avz_stream_args {
+  int streams, hops;                 /* hops >= 1 new hops per stream in this call            */
+  double forget;
+  const int* active;                 /* device [streams] or NULL: 0 = stream skipped, its state
+                                        and its rows of out untouched                        */
+  const int* adapt;                  /* device [streams] or NULL = all adapt                  */
+  const float* mix;  long long mix_stride, ch_stride;      /* [streams][2][hops*hop]         */
+  const float* ref_tgt; const float* ref_int; long long ref_stride;   /* IBM                  */
+  const float* ext_mask; long long mask_stride_b, mask_stride_f, mask_stride_t; /* [s][F][hops] */
+  float* out; long long out_stride;  /* [streams][hops*hop], 16-byte aligned, stride % 4 == 0 */
+  float* w_out;  double* cov_out;    /* optional: weights [streams][F][4] / sums [streams][F][5]
+                                        after the call's last frame                          */
+  float* mask_out;                   /* optional debug: n_t used, [streams][F][hops] contiguous */
+  void* state; long long state_bytes;
+} avz_stream_args;
+int avz_stream_push(const avz_plan* plan, const avz_stream_args* args, void* hip_stream);
+
 const char* avz_strerror(int code);
 /* Last HIP error string recorded by the library on this thread (diagnostics). */
 const char* avz_last_hip_error(void);

@@ -47,6 +47,7 @@ EXPORTED = [
     "avz_scene_reverb_generate",
     "avz_stoi_workspace_bytes", "avz_stoi_batch",
     "avz_mask_training_batch",
+    "avz_stream_state_bytes", "avz_stream_reset", "avz_stream_steer", "avz_stream_push",
 ]
 
 
@@ -112,6 +113,20 @@ class AvzStoiArgs(ct.Structure):
         ("resampled", ct.c_void_p), ("res_stride", ct.c_longlong),
         ("tob", ct.c_void_p), ("tob_stride", ct.c_longlong),
         ("workspace", ct.c_void_p), ("workspace_bytes", ct.c_longlong),
+    ]
+
+
+class AvzStreamArgs(ct.Structure):
+    _fields_ = [
+        ("streams", ct.c_int), ("hops", ct.c_int), ("forget", ct.c_double),
+        ("active", ct.c_void_p), ("adapt", ct.c_void_p),
+        ("mix", ct.c_void_p), ("mix_stride", ct.c_longlong), ("ch_stride", ct.c_longlong),
+        ("ref_tgt", ct.c_void_p), ("ref_int", ct.c_void_p), ("ref_stride", ct.c_longlong),
+        ("ext_mask", ct.c_void_p), ("mask_stride_b", ct.c_longlong),
+        ("mask_stride_f", ct.c_longlong), ("mask_stride_t", ct.c_longlong),
+        ("out", ct.c_void_p), ("out_stride", ct.c_longlong),
+        ("w_out", ct.c_void_p), ("cov_out", ct.c_void_p), ("mask_out", ct.c_void_p),
+        ("state", ct.c_void_p), ("state_bytes", ct.c_longlong),
     ]
 
 
@@ -212,6 +227,21 @@ def _load():
     lib.avz_mask_training_batch.argtypes = [P, I, I, P, I, P, LL, LL, P, P, LL, P, LL, LL, LL, LL,
                                             P, LL, LL, LL, P]
     lib.avz_mask_training_batch.restype = ct.c_int
+    SA = ct.POINTER(AvzStreamArgs)
+    CP = ct.POINTER(AvzConfig)
+    lib.avz_stream_state_bytes.argtypes = [P, I]
+    lib.avz_stream_state_bytes.restype = LL
+    lib.avz_stream_reset.argtypes = [P, P, LL, I, P, P]
+    lib.avz_stream_steer.argtypes = [P, P, LL, I, P, P]
+    lib.avz_stream_push.argtypes = [P, SA, P]
+    # the same host-side checks on a bare configuration (no plan, no device; tests)
+    lib.avz_stream_check_state_bytes.argtypes = [CP, I]
+    lib.avz_stream_check_state_bytes.restype = LL
+    lib.avz_stream_check_state.argtypes = [CP, P, LL, I, P, I]
+    lib.avz_stream_check_push.argtypes = [CP, SA]
+    for name in ("avz_stream_reset", "avz_stream_steer", "avz_stream_push",
+                 "avz_stream_check_state", "avz_stream_check_push"):
+        getattr(lib, name).restype = ct.c_int
     lib.avz_stoi_taps.argtypes = [DP]
     lib.avz_stoi_taps.restype = ct.c_int
     lib.avz_strerror.argtypes = [ct.c_int]

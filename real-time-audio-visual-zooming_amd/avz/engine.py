@@ -14,7 +14,7 @@ from dataclasses import dataclass, field
 import torch
 
 from . import _lib
-from ._lib import AvzBatchArgs, AvzConfig, check, lib
+from ._lib import AvzBatchArgs, AvzConfig, AvzStreamArgs, check, lib
 
 MASKS = {"ibm": _lib.MASK_IBM, "ipd": _lib.MASK_IPD, "external": _lib.MASK_EXTERNAL,
          "ones": _lib.MASK_ONES}
@@ -479,6 +479,73 @@ def mask_training_batch(plan: MVDRPlan, mix: torch.Tensor, tgt: torch.Tensor, it
         ct.c_void_p(label.data_ptr()), label.stride(0), label.stride(1), label.stride(2),
         _stream_handle(stream)), "avz_mask_training_batch")
     return feat, label
+
+
+# ------------------------------------------------------------------ streaming causal MVDR
+# Thin wrappers over avz_stream_* (include/avz.h); avz/stream.py StreamingBeamformer owns the
+# state buffer and is the interface to use.
+def stream_state_bytes(plan: MVDRPlan, streams: int) -> int:
+    return check(lib.avz_stream_state_bytes(plan._h, int(streams)), "avz_stream_state_bytes")
+
+
+def stream_reset(plan: MVDRPlan, state: torch.Tensor, streams: int, select=None, stream=None):
+    """Zero the selected streams (select: int32 [streams] device tensor, None = all) and give
+    them the plan's steering table."""
+    check(lib.avz_stream_reset(plan._h, _ptr(state), state.numel(), int(streams), _ptr(select),
+                               _stream_handle(stream)), "avz_stream_reset")
+
+
+def stream_steer(plan: MVDRPlan, state: torch.Tensor, streams: int, angles: torch.Tensor,
+                 stream=None):
+    """angles: float64 [streams] device tensor, degrees; NaN keeps a stream's direction."""
+    check(lib.avz_stream_steer(plan._h, _ptr(state), state.numel(), int(streams), _ptr(angles),
+                               _stream_handle(stream)), "avz_stream_steer")
+
+
+def stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out: torch.Tensor, *,
+                forget: float = 1.0, ref_tgt=None, ref_int=None, mask=None, active=None,
+                adapt=None, w_out=None, cov_out=None, mask_out=None, stream=None):
+    """One avz_stream_push: mix [streams, 2, hops * hop] -> out [streams, hops * hop] (float32
+    device tensors, samples contiguous). mask [streams, F, hops] (external plans), ref_tgt /
+    ref_int [streams, hops * hop] sharing a row stride (IBM plans); active / adapt int32
+    [streams]; w_out [streams, F, 4] float32, cov_out [streams, F, 5] float64 and mask_out
+    [streams, F, hops] float32 contiguous."""
+    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or \
+            mix.stride(2) != 1 or not mix.is_cuda:
+        raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
+    streams, _, n = mix.shape
+    if n == 0 or n % plan.hop:
+        raise ValueError("mix must hold a whole number (>= 1) of hops")
+    hops = n // plan.hop
+    if out.dtype != torch.float32 or tuple(out.shape) != (streams, n) or out.stride(1) != 1:
+        raise ValueError("out must be float32 [streams, hops * hop]")
+    a = AvzStreamArgs()
+    a.streams, a.hops, a.forget = streams, hops, float(forget)
+    a.active, a.adapt = _ptr(active), _ptr(adapt)
+    a.mix, a.mix_stride, a.ch_stride = _ptr(mix), mix.stride(0), mix.stride(1)
+    if ref_tgt is not None or ref_int is not None:
+        for name, r in (("ref_tgt", ref_tgt), ("ref_int", ref_int)):
+            if r is None or tuple(r.shape) != (streams, n) or r.dtype != torch.float32 or \
+                    r.stride(1) != 1:
+                raise ValueError(f"{name} must be float32 [streams, hops * hop]")
+        if ref_int.stride(0) != ref_tgt.stride(0):
+            raise ValueError("ref_tgt and ref_int must share a stride")
+        a.ref_tgt, a.ref_int, a.ref_stride = _ptr(ref_tgt), _ptr(ref_int), ref_tgt.stride(0)
+    if mask is not None:
+        if tuple(mask.shape) != (streams, plan.F, hops) or mask.dtype != torch.float32:
+            raise ValueError("mask must be float32 [streams, F, hops]")
+        a.ext_mask = _ptr(mask)
+        a.mask_stride_b, a.mask_stride_f, a.mask_stride_t = mask.stride()
+    a.out, a.out_stride = _ptr(out), out.stride(0)
+    for name, t, shape, dt in (("w_out", w_out, (streams, plan.F, 4), torch.float32),
+                               ("cov_out", cov_out, (streams, plan.F, 5), torch.float64),
+                               ("mask_out", mask_out, (streams, plan.F, hops), torch.float32)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}")
+    a.w_out, a.cov_out, a.mask_out = _ptr(w_out), _ptr(cov_out), _ptr(mask_out)
+    a.state, a.state_bytes = _ptr(state), state.numel()
+    check(lib.avz_stream_push(plan._h, ct.byref(a), _stream_handle(stream)), "avz_stream_push")
+    return out
 
 
 def srp_scan(plan: MVDRPlan, mix: torch.Tensor, lengths=None, max_len=None, n_angles=181,

@@ -1274,3 +1274,143 @@ extern "C" int avz_projection_metrics(int batch, int max_len, const int* len, co
   return avz_projection_metrics_scaled(batch, max_len, len, est, est_stride, nullptr, 0.0, tgt,
                                        tgt_stride, itf, itf_stride, sums, metrics, stream);
 }
+
+// ------------------------------------------------------------------ streaming causal MVDR
+// Every check below runs on the host from the plan's configuration alone, before any HIP
+// call. The avz_stream_check_* forms take the configuration itself, so they can be exercised
+// without a device (tests); the public entry points call them with the plan's.
+static int stream_config_check(const avz_config& c) {
+  if (c.beamformer != AVZ_BF_MVDR || c.mask_mode == AVZ_MASK_IPD ||
+      c.postfilter == AVZ_PF_IRM || c.singular_fallback == AVZ_FALLBACK_BATCH ||
+      c.normalize != AVZ_NORM_NONE)
+    return AVZ_ERR_UNSUPPORTED;
+  return AVZ_OK;
+}
+
+extern "C" long long avz_stream_check_state_bytes(const avz_config* c, int streams) {
+  if (!c) return AVZ_ERR_ARG;
+  const int rc = stream_config_check(*c);
+  if (rc != AVZ_OK) return rc;
+  if (streams < 1 || streams > c->max_batch) return AVZ_ERR_SHAPE;
+  return avz::StreamLayout(c->n_fft).stride * streams;
+}
+
+// The state buffer of a reset / steer / push call.
+static int stream_state_check(const avz_config& c, const void* state, long long state_bytes,
+                              int streams) {
+  const int rc = stream_config_check(c);
+  if (rc != AVZ_OK) return rc;
+  if (!state) return AVZ_ERR_ARG;
+  if (streams < 1 || streams > c.max_batch) return AVZ_ERR_SHAPE;
+  if (state_bytes < avz::StreamLayout(c.n_fft).stride * streams) return AVZ_ERR_SHAPE;
+  if (misaligned(state, 256)) return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+extern "C" int avz_stream_check_state(const avz_config* c, const void* state,
+                                      long long state_bytes, int streams, const void* per_stream,
+                                      int per_stream_required) {
+  if (!c) return AVZ_ERR_ARG;
+  const int rc = stream_config_check(*c);
+  if (rc != AVZ_OK) return rc;
+  if (per_stream_required && !per_stream) return AVZ_ERR_ARG;
+  return stream_state_check(*c, state, state_bytes, streams);
+}
+
+extern "C" int avz_stream_check_push(const avz_config* cfg, const avz_stream_args* a) {
+  if (!cfg || !a) return AVZ_ERR_ARG;
+  const avz_config& c = *cfg;
+  int rc = stream_config_check(c);
+  if (rc != AVZ_OK) return rc;
+  if (!a->mix || !a->out || !a->state) return AVZ_ERR_ARG;
+  if (c.mask_mode == AVZ_MASK_IBM && (!a->ref_tgt || !a->ref_int)) return AVZ_ERR_ARG;
+  if (c.mask_mode == AVZ_MASK_EXTERNAL && !a->ext_mask) return AVZ_ERR_ARG;
+  if (a->hops < 1) return AVZ_ERR_ARG;
+  if (!(a->forget > 0.0 && a->forget <= 1.0)) return AVZ_ERR_ARG;  // NaN included
+  if (a->streams < 1 || a->streams > c.max_batch) return AVZ_ERR_SHAPE;
+  const long long row = (long long)a->hops * c.hop;
+  if (row > (1LL << 30)) return AVZ_ERR_SHAPE;
+  if (a->ch_stride < row || a->out_stride < row) return AVZ_ERR_SHAPE;
+  if (a->streams > 1 && a->mix_stride < a->ch_stride + row) return AVZ_ERR_SHAPE;
+  if (c.mask_mode == AVZ_MASK_IBM && a->streams > 1 && a->ref_stride < row) return AVZ_ERR_SHAPE;
+  rc = stream_state_check(c, a->state, a->state_bytes, a->streams);
+  if (rc != AVZ_OK) return rc;
+  if (misaligned(a->out, 16) || (a->out_stride & 3)) return AVZ_ERR_ALIGN;
+  if (misaligned(a->mix, 4) || misaligned(a->ref_tgt, 4) || misaligned(a->ref_int, 4) ||
+      misaligned(a->ext_mask, 4) || misaligned(a->w_out, 4) || misaligned(a->cov_out, 8) ||
+      misaligned(a->mask_out, 4))
+    return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+extern "C" long long avz_stream_state_bytes(const avz_plan* p, int streams) {
+  if (!p) return AVZ_ERR_ARG;
+  return avz_stream_check_state_bytes(&p->cfg, streams);
+}
+
+extern "C" int avz_stream_reset(const avz_plan* p, void* state, long long state_bytes,
+                                int streams, const int* select, void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = avz_stream_check_state(&p->cfg, state, state_bytes, streams, nullptr, 0);
+  if (rc != AVZ_OK) return rc;
+  avz::StreamArgs s{};
+  s.streams = streams;
+  s.state = static_cast<unsigned char*>(state);
+  s.state_stride = avz::StreamLayout(p->cfg.n_fft).stride;
+  s.select = select;
+  rc = avz_launch_stream_reset(p->cfg.n_fft, &s, p->steer, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+extern "C" int avz_stream_steer(const avz_plan* p, void* state, long long state_bytes,
+                                int streams, const double* angle_deg, void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = avz_stream_check_state(&p->cfg, state, state_bytes, streams, angle_deg, 1);
+  if (rc != AVZ_OK) return rc;
+  if (misaligned(angle_deg, 8)) return AVZ_ERR_ALIGN;
+  avz::StreamArgs s{};
+  s.streams = streams;
+  s.state = static_cast<unsigned char*>(state);
+  s.state_stride = avz::StreamLayout(p->cfg.n_fft).stride;
+  s.angle_deg = angle_deg;
+  rc = avz_launch_stream_steer(p->cfg.n_fft, &s, p->cfg.mic_d, p->cfg.c_sound, (double)p->cfg.fs,
+                               stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+extern "C" int avz_stream_push(const avz_plan* p, const avz_stream_args* a, void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = avz_stream_check_push(&p->cfg, a);
+  if (rc != AVZ_OK) return rc;
+  const avz_config& c = p->cfg;
+  avz::ChainArgs k{};
+  plan_params(p, k);
+  avz::StreamArgs s{};
+  s.streams = a->streams;
+  s.hops = a->hops;
+  s.forget = a->forget;
+  s.active = a->active;
+  s.adapt = a->adapt;
+  s.mix = a->mix;
+  s.mix_stride = a->mix_stride;
+  s.ch_stride = a->ch_stride;
+  s.ref_tgt = a->ref_tgt;
+  s.ref_int = a->ref_int;
+  s.ref_stride = a->ref_stride;
+  s.ext_mask = a->ext_mask;
+  s.mask_sb = a->mask_stride_b;
+  s.mask_sf = a->mask_stride_f;
+  s.mask_st = a->mask_stride_t;
+  s.out = a->out;
+  s.out_stride = a->out_stride;
+  s.w_out = a->w_out;
+  s.cov_out = a->cov_out;
+  s.mask_out = a->mask_out;
+  s.state = static_cast<unsigned char*>(a->state);
+  s.state_stride = avz::StreamLayout(c.n_fft).stride;
+  rc = avz_launch_stream_push(c.n_fft, c.mask_mode, &s, &k, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}

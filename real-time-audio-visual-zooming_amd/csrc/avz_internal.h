@@ -243,6 +243,47 @@ struct TrainArgs {
   long long l_sb, l_sf, l_st;
 };
 
+// Streaming causal MVDR (avz_stream_push / _reset / _steer, avz_stream.hip). The per-stream
+// state block (private layout; StreamLayout) is caller-owned device memory.
+struct StreamArgs {
+  int streams, hops;
+  double forget;
+  const int* active;          // [streams] or null: 0 = the stream is skipped
+  const int* adapt;           // [streams] or null: 0 = the sums (and so the weights) freeze
+  const float* mix;           // [streams][2][hops * H] planar
+  long long mix_stride, ch_stride;
+  const float* ref_tgt;       // [streams][hops * H] (IBM) or null
+  const float* ref_int;
+  long long ref_stride;
+  const float* ext_mask;      // target probability M[s][k][j], j = hop of this call, or null
+  long long mask_sb, mask_sf, mask_st;
+  float* out;                 // [streams][hops * H]
+  long long out_stride;
+  float* w_out;               // [streams][F][4] or null
+  double* cov_out;            // [streams][F][5] or null
+  float* mask_out;            // [streams][F][hops] or null: the noise weight used
+  unsigned char* state;       // [streams][state_stride bytes]
+  long long state_stride;
+  const int* select;          // reset: [streams] or null = all
+  const double* angle_deg;    // steer: [streams], NaN = keep
+};
+
+// Bytes of one stream's state block for n_fft = N (H = N / 2, F = H + 1): the frame count
+// (64-bit, in a 64-byte header), the previous hop of mic 0, mic 1, target and interference
+// reference [4][H] f32, the synthesis tail g[H:] [H] f32, the sums c[F][5] f64 and the
+// steering table [F][4] f64 (d0 re, im, d1 re, im); rounded up to 256 bytes.
+struct StreamLayout {
+  long long prev_off = 0, tail_off = 0, cov_off = 0, steer_off = 0, stride = 0;
+  constexpr explicit StreamLayout(int n_fft) {  // constexpr: host and device
+    const long long H = n_fft / 2, F = H + 1;
+    prev_off = 64;
+    tail_off = prev_off + 4 * H * 4;
+    cov_off = tail_off + H * 4;
+    steer_off = cov_off + F * 5 * 8;
+    stride = (steer_off + F * 4 * 8 + 255) & ~255LL;
+  }
+};
+
 struct SrpArgs {
   int n_angles;
   double angle_lo, angle_hi;  // np.linspace(angle_lo, angle_hi, n_angles)
@@ -357,4 +398,10 @@ int avz_launch_srp(int n_fft, const avz::ChainArgs* a, const avz::SrpArgs* s, vo
 int avz_chunk_frames(void);
 int avz_launch_stft(int n_fft, const avz::StftArgs* a, void* stream);
 int avz_launch_train(int n_fft, const avz::TrainArgs* a, void* stream);
+int avz_launch_stream_push(int n_fft, int mask_mode, const avz::StreamArgs* s,
+                           const avz::ChainArgs* p, void* stream);
+int avz_launch_stream_reset(int n_fft, const avz::StreamArgs* s, const double* plan_steer,
+                            void* stream);
+int avz_launch_stream_steer(int n_fft, const avz::StreamArgs* s, double mic_d, double c_sound,
+                            double fs, void* stream);
 }

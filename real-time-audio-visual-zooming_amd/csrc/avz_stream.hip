@@ -1,0 +1,352 @@
+// avz_stream.hip — streaming causal MVDR (avz_stream_push, avz_stream_reset, avz_stream_steer):
+// the chain of avz_mvdr_batch run hop by hop, with the masked covariance as a recursion
+// c_t = forget c_{t-1} + n_t (|y0|^2, |y1|^2, Re y0 y1*, Im y0 y1*, 1) and the weights solved
+// from c_t for every frame (avz/stream.py stream_numpy restates it).
+//
+// Layout: one 256-thread block per stream, resident for the whole call; the block walks the
+// call's hops in groups of the eight frames its eight lane groups hold (KCfg<N>: two 32-lane
+// transforms per wave, the STFT kernels' slots). Per group:
+//   (IBM) packed reference transforms tgt + i itf -> one noise bit per (bin, frame) in LDS;
+//   packed mic transforms mic0 + i mic1 into the slots;
+//   per bin (thread k, k + 256, ..): the recursion over the group's frames in order, the fp64
+//     solve (mvdr_weights_d), S = w^H y times the post-filter gain, written over Z[k] with its
+//     Hermitian mirror over Z[N - k];
+//   one inverse transform per lane group (conj FFT conj of the Hermitian spectrum: the real
+//     part is irfft N), times sum(w) w[n], stored as N floats in the slot;
+//   overlap-add of each frame's first half with its predecessor's second half (the state's
+//     tail for the group's first frame), divided by w^2[m] + w^2[m + H], float4 stores.
+// A frame's arithmetic is the same instruction sequence whatever its slot, group or call and
+// reads nothing of another stream, so a stream's results do not depend on how its hops are
+// grouped into calls, on its index or on the other streams. No atomics, no inter-block
+// traffic. Four of a call's frames could share two packed inverse transforms, but with one
+// block per stream the four waves sit on four SIMDs and a wave's second lane group is free:
+// one inverse per lane group has the same latency.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "avz_common.hpp"
+
+namespace avz {
+
+constexpr int kStreamThreads = 256;
+
+template <int N>
+struct StreamGeo {
+  using C = KCfg<N>;
+  using G = Geo<N, kStreamThreads>;
+  static constexpr int H = N / 2, F = N / 2 + 1;
+  static constexpr int NSLOT = G::NSLOT;  // 8 frames per group
+  // LDS map: [FFT slots][twiddles][window N f32][tail H f32][noise bits F u32]
+  static constexpr int TW_OFF = G::SLOT_LDS;
+  static constexpr int WIN_OFF = TW_OFF + C::TW_BYTES;
+  static constexpr int TAIL_OFF = WIN_OFF + N * 4;
+  static constexpr int BITS_OFF = TAIL_OFF + H * 4;
+  static constexpr int LDS_BYTES = BITS_OFF + ((F * 4 + 15) & ~15);
+  static_assert(NSLOT == 8, "eight frame slots per 256-thread block");
+  static_assert(C::GROUP_BYTES >= N * 8, "a slot holds a whole spectrum");
+  static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+};
+
+// Windowed forward transform of the packed pair re + i im of hop j's frame [x_{j-1} | x_j]
+// into the lane group's slot. Sample q = j H - H + n of the call's rows; q < 0 is the state's
+// previous hop. A slot beyond the group's frames transforms zeros.
+template <int N>
+__device__ __forceinline__ void stream_transform(const typename KCfg<N>::Fft& fft,
+                                                 const LaneMap<N>& lm, const float* re,
+                                                 const float* im, const float* pre,
+                                                 const float* pim, int j, bool valid,
+                                                 const float* win, cf* spec, const cf* twid) {
+  using C = KCfg<N>;
+  constexpr int PPL = C::PPL, H = N / 2;
+  cf v[PPL];
+  static_for<0, PPL>([&](auto r) {
+    const int n = lm.in0 + C::IN_STRIDE * r;
+    const long long q = (long long)j * H - H + n;
+    float a = 0.0f, b = 0.0f;
+    if (valid) {
+      a = q < 0 ? pre[q + H] : re[q];
+      b = q < 0 ? pim[q + H] : im[q];
+    }
+    const float w = win[n] * (2.0f / N);  // 1 / sum(w): exact scaling
+    v[r] = {a * w, b * w};
+  });
+  __builtin_amdgcn_wave_barrier();
+  fft.forward(v, spec, twid);
+  static_for<0, PPL>([&](auto k) { spec[lm.out0 + C::OUT_STRIDE * k] = v[k]; });
+}
+
+template <int N, int MASK>
+__global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArgs S, ChainArgs P) {
+  using C = KCfg<N>;
+  using SG = StreamGeo<N>;
+  constexpr int H = SG::H, F = SG::F, NSLOT = SG::NSLOT;
+  const int s = blockIdx.x;
+  if (S.active && S.active[s] == 0) return;
+  extern __shared__ __align__(16) unsigned char lds[];
+  cf* twid = reinterpret_cast<cf*>(lds + SG::TW_OFF);
+  float* win = reinterpret_cast<float*>(lds + SG::WIN_OFF);
+  float* tail = reinterpret_cast<float*>(lds + SG::TAIL_OFF);
+  uint32_t* nbits = reinterpret_cast<uint32_t*>(lds + SG::BITS_OFF);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+
+  const StreamLayout lay(N);
+  unsigned char* st = S.state + (long long)s * S.state_stride;
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(st);
+  float* prev = reinterpret_cast<float*>(st + lay.prev_off);  // [4][H]
+  float* tail_g = reinterpret_cast<float*>(st + lay.tail_off);
+  double* cov = reinterpret_cast<double*>(st + lay.cov_off);
+  const double* steer = reinterpret_cast<const double*>(st + lay.steer_off);
+  const unsigned long long count0 = *cnt;
+  const bool adapt = !S.adapt || S.adapt[s] != 0;
+  const double lam = S.forget;
+
+  C::Fft::fill_twiddles(twid, tid, kStreamThreads);
+  for (int n = tid; n < N; n += kStreamThreads) win[n] = P.xwin[n];
+  for (int m = tid; m < H; m += kStreamThreads) tail[m] = tail_g[m];
+  __syncthreads();
+
+  typename C::Fft fft;
+  fft.init(lane);
+  LaneMap<N> lm;
+  lm.init(lane);
+  const int my_slot = wave * C::FPW + lm.grp;
+  cf* spec = slot_ptr<N>(lds, my_slot);
+
+  const float* x0 = S.mix + (long long)s * S.mix_stride;
+  const float* x1 = x0 + S.ch_stride;
+  const float* rt = MASK == MASK_IBM ? S.ref_tgt + (long long)s * S.ref_stride : nullptr;
+  const float* ri = MASK == MASK_IBM ? S.ref_int + (long long)s * S.ref_stride : nullptr;
+  float* orow = S.out + (long long)s * S.out_stride;
+
+  for (int j0 = 0; j0 < S.hops; j0 += NSLOT) {
+    const int nf = min(NSLOT, S.hops - j0);
+    const bool valid = my_slot < nf;
+    const bool last = j0 + nf == S.hops;
+
+    if constexpr (MASK == MASK_IBM) {
+      // reference pair -> noise bits: bit f of nbits[k] = frame j0 + f of bin k is noise
+      stream_transform<N>(fft, lm, rt, ri, prev + 2 * H, prev + 3 * H, j0 + my_slot, valid, win,
+                          spec, twid);
+      __syncthreads();
+      for (int k = tid; k < F; k += kStreamThreads) {
+        uint32_t bits = 0;
+        for (int f = 0; f < nf; ++f) {
+          const cf* Z = slot_ptr<N>(lds, f);
+          // noise <=> |S_i| > |S_t| <=> Re(Z[k] Z[N - k]) < 0 (avz_chunked_k.hpp ibm_noise)
+          const cf z = Z[k], zp = Z[(N - k) & (N - 1)];
+          bits |= (fmaf(z.x, zp.x, -(z.y * zp.y)) < 0.0f ? 1u : 0u) << f;
+        }
+        nbits[k] = bits;
+      }
+      __syncthreads();  // every slot has been read before its lane group overwrites it
+    }
+
+    stream_transform<N>(fft, lm, x0, x1, prev, prev + H, j0 + my_slot, valid, win, spec, twid);
+    __syncthreads();
+
+    // per bin: recursion, solve and apply over the group's frames, in order
+    for (int k = tid; k < F; k += kStreamThreads) {
+      const int kp = (N - k) & (N - 1);
+      double c[5], w[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int i = 0; i < 5; ++i) c[i] = cov[5 * k + i];
+      const double d0r = steer[4 * k], d0i = steer[4 * k + 1];
+      const double d1r = steer[4 * k + 2], d1i = steer[4 * k + 3];
+      const uint32_t bits = MASK == MASK_IBM ? nbits[k] : 0u;
+      for (int f = 0; f < nf; ++f) {
+        cf* Z = slot_ptr<N>(lds, f);
+        const cf z = Z[k], zp = Z[kp];
+        cf y0, y1;
+        split_pair(z, zp, y0, y1);
+        float nw, wgt, M = 1.0f;  // noise weight, covariance weight, target probability
+        if constexpr (MASK == MASK_IBM) {
+          nw = ((bits >> f) & 1u) ? 1.0f : 0.0f;
+          wgt = nw;
+        } else if constexpr (MASK == MASK_EXTERNAL) {
+          M = S.ext_mask[(long long)s * S.mask_sb + (long long)k * S.mask_sf +
+                         (long long)(j0 + f) * S.mask_st];
+          nw = 1.0f - M;
+          wgt = nw + P.weight_eps;
+        } else {
+          nw = 1.0f;
+          wgt = 1.0f;
+        }
+        if (adapt) {
+          const double ar = y0.x, ai = y0.y, er = y1.x, ei = y1.y, wg = wgt;
+          c[0] = fma(wg, ar * ar + ai * ai, lam * c[0]);
+          c[1] = fma(wg, er * er + ei * ei, lam * c[1]);
+          c[2] = fma(wg, ar * er + ai * ei, lam * c[2]);  // Re y0 conj(y1)
+          c[3] = fma(wg, ai * er - ar * ei, lam * c[3]);  // Im y0 conj(y1)
+          c[4] = lam * c[4] + (double)nw;
+        }
+        mvdr_weights_d(c, k, N, P, d0r, d0i, d1r, d1i, w, nullptr);
+        cf alpha, beta;
+        coef_from_w(w[0], w[1], w[2], w[3], alpha, beta, nullptr);
+        float g = 1.0f;
+        if (P.postfilter == PF_IBM_TARGET) g = 1.0f - nw;
+        else if (P.postfilter == PF_EXT_FLOOR) g = fmaxf(M, P.pf_floor);
+        else if (P.postfilter == PF_EXT_MUL) g = M;
+        const cf sv = apply_bin(alpha, beta, z, zp, g);
+        if (kp == k) {
+          Z[k] = {sv.x, 0.0f};  // DC / Nyquist: irfft reads the real part only
+        } else {
+          Z[k] = sv;
+          Z[kp] = c_conj(sv);
+        }
+        if (S.mask_out)
+          S.mask_out[((long long)s * F + k) * S.hops + (j0 + f)] = nw;
+      }
+#pragma unroll
+      for (int i = 0; i < 5; ++i) cov[5 * k + i] = c[i];
+      if (last) {
+        if (S.cov_out) {
+#pragma unroll
+          for (int i = 0; i < 5; ++i) S.cov_out[((long long)s * F + k) * 5 + i] = c[i];
+        }
+        if (S.w_out) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) S.w_out[((long long)s * F + k) * 4 + i] = (float)w[i];
+        }
+      }
+    }
+    __syncthreads();
+
+    // inverse transform of each frame in its own slot: g = irfft(S) sum(w) w = Re(.) / 2 w
+    {
+      cf v[C::PPL];
+      static_for<0, C::PPL>(
+          [&](auto r) { v[r] = c_conj(spec[lm.in0 + C::IN_STRIDE * r]); });
+      __builtin_amdgcn_wave_barrier();  // the group's reads precede the transform's stores
+      fft.forward(v, spec, twid);
+      float* gf = reinterpret_cast<float*>(spec);
+      static_for<0, C::PPL>([&](auto k) {
+        const int n = lm.out0 + C::OUT_STRIDE * k;
+        gf[n] = (0.5f * v[k].x) * win[n];
+      });
+    }
+    __syncthreads();
+
+    // overlap-add: hop j = (g_{j-1}[H:] + g_j[:H]) / (w^2[m] + w^2[m + H]); the stream's
+    // first hop is zeros
+    for (int idx = tid; idx < nf * (H / 4); idx += kStreamThreads) {
+      const int f = idx / (H / 4), m = (idx % (H / 4)) * 4;
+      const float* gc = reinterpret_cast<const float*>(slot_ptr<N>(lds, f)) + m;
+      const float* gp =
+          f == 0 ? tail + m : reinterpret_cast<const float*>(slot_ptr<N>(lds, f - 1)) + H + m;
+      const bool first = count0 + (unsigned long long)(j0 + f) == 0ull;
+      float o[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float w0 = win[m + i], w1 = win[m + i + H];
+        const float den = fmaf(w1, w1, w0 * w0);
+        o[i] = first ? 0.0f : (gp[i] + gc[i]) / den;
+      }
+      *reinterpret_cast<float4*>(orow + (long long)(j0 + f) * H + m) =
+          make_float4(o[0], o[1], o[2], o[3]);
+    }
+    __syncthreads();
+    for (int m = tid; m < H; m += kStreamThreads)
+      tail[m] = reinterpret_cast<const float*>(slot_ptr<N>(lds, nf - 1))[H + m];
+    __syncthreads();
+  }
+
+  // the state after the call's last frame
+  const long long qlast = (long long)(S.hops - 1) * H;
+  for (int m = tid; m < H; m += kStreamThreads) {
+    tail_g[m] = tail[m];
+    prev[m] = x0[qlast + m];
+    prev[H + m] = x1[qlast + m];
+    if constexpr (MASK == MASK_IBM) {
+      prev[2 * H + m] = rt[qlast + m];
+      prev[3 * H + m] = ri[qlast + m];
+    }
+  }
+  if (tid == 0) *cnt = count0 + (unsigned long long)S.hops;
+}
+
+// Zero the selected streams' state and copy the plan's steering table into them.
+__global__ void __launch_bounds__(kStreamThreads) avz_stream_reset_kernel(StreamArgs S, int n_fft,
+                                                                          const double* steer) {
+  const int s = blockIdx.x;
+  if (S.select && S.select[s] == 0) return;
+  const StreamLayout lay(n_fft);
+  unsigned char* st = S.state + (long long)s * S.state_stride;
+  uint32_t* words = reinterpret_cast<uint32_t*>(st);
+  const int n_zero = (int)(lay.steer_off / 4);
+  for (int i = threadIdx.x; i < n_zero; i += kStreamThreads) words[i] = 0u;
+  double* d = reinterpret_cast<double*>(st + lay.steer_off);
+  const int n_steer = (n_fft / 2 + 1) * 4;
+  for (int i = threadIdx.x; i < n_steer; i += kStreamThreads) d[i] = steer[i];
+}
+
+// masked_mvdr.get_steering_vector for the stream's new angle: tau1 = (d/2) cos(theta) / c,
+// tau2 = (d/2) cos(theta - pi) / c, d_m = exp(-2 pi i f_k tau_m); cospi / sincospi keep the
+// argument reduction exact and free of tables.
+__global__ void __launch_bounds__(kStreamThreads) avz_stream_steer_kernel(StreamArgs S, int n_fft,
+                                                                          double mic_d,
+                                                                          double c_sound,
+                                                                          double fs) {
+  const int s = blockIdx.x;
+  const double ang = S.angle_deg[s];
+  if (ang != ang) return;  // NaN: keep
+  const StreamLayout lay(n_fft);
+  double* d = reinterpret_cast<double*>(S.state + (long long)s * S.state_stride + lay.steer_off);
+  const double tau1 = (mic_d / 2) * cospi(ang / 180.0) / c_sound;
+  const double tau2 = (mic_d / 2) * cospi(ang / 180.0 - 1.0) / c_sound;
+  for (int k = threadIdx.x; k < n_fft / 2 + 1; k += kStreamThreads) {
+    const double fk = (double)k * fs / (double)n_fft;
+    double sn, cs;
+    sincospi(2.0 * fk * tau1, &sn, &cs);
+    d[4 * k + 0] = cs;
+    d[4 * k + 1] = -sn;
+    sincospi(2.0 * fk * tau2, &sn, &cs);
+    d[4 * k + 2] = cs;
+    d[4 * k + 3] = -sn;
+  }
+}
+
+}  // namespace avz
+
+using namespace avz;
+
+template <int N, int MASK>
+static int launch_stream_t(const StreamArgs* s, const ChainArgs* p, hipStream_t st) {
+  auto kern = avz_stream_kernel<N, MASK>;
+  const int lds = StreamGeo<N>::LDS_BYTES;
+  if (!lds_ready<avz_stream_kernel<N, MASK>>(lds)) return -3;
+  hipLaunchKernelGGL(kern, dim3(s->streams), dim3(kStreamThreads), lds, st, *s, *p);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+template <int N>
+static int launch_stream_n(int mask_mode, const StreamArgs* s, const ChainArgs* p,
+                           hipStream_t st) {
+  switch (mask_mode) {
+    case MASK_IBM: return launch_stream_t<N, MASK_IBM>(s, p, st);
+    case MASK_EXTERNAL: return launch_stream_t<N, MASK_EXTERNAL>(s, p, st);
+    case MASK_ONES: return launch_stream_t<N, MASK_ONES>(s, p, st);
+  }
+  return -4;
+}
+
+extern "C" int avz_launch_stream_push(int n_fft, int mask_mode, const StreamArgs* s,
+                                      const ChainArgs* p, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (n_fft == 1024) return launch_stream_n<1024>(mask_mode, s, p, st);
+  if (n_fft == 512) return launch_stream_n<512>(mask_mode, s, p, st);
+  return -4;
+}
+
+extern "C" int avz_launch_stream_reset(int n_fft, const StreamArgs* s, const double* plan_steer,
+                                       void* stream) {
+  hipLaunchKernelGGL(avz_stream_reset_kernel, dim3(s->streams), dim3(kStreamThreads), 0,
+                     (hipStream_t)stream, *s, n_fft, plan_steer);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+extern "C" int avz_launch_stream_steer(int n_fft, const StreamArgs* s, double mic_d,
+                                       double c_sound, double fs, void* stream) {
+  hipLaunchKernelGGL(avz_stream_steer_kernel, dim3(s->streams), dim3(kStreamThreads), 0,
+                     (hipStream_t)stream, *s, n_fft, mic_d, c_sound, fs);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
