@@ -355,7 +355,17 @@ int avz_mask_training_batch(const avz_plan* plan, int layout, int batch, const i
 /* Steered response power scan, scripts/debug_srp.py:46-62 for a batch: for the
  * angles np.linspace(angle_lo, angle_hi, n_angles) (degrees, the plan's mic_d and
  * c_sound, debug_srp.py:17-23 geometry), P = sum over bins f_lo <= f <= f_hi and all
- * frames of |d^H y|^2; power_db[b][i] = 10 log10(P_i) - max_j 10 log10(P_j) (device). */
+ * frames of |d^H y|^2; power_db[b][i] = 10 log10(P_i) - max_j 10 log10(P_j) (device).
+ * Both band edges are inclusive (f_k = k fs / n_fft compared in fp64). n_angles = 1 scans
+ * angle_lo alone and gives exactly 0.0; n_angles is not limited by the block size. The plan's
+ * mask mode is irrelevant (the scan sums the unmasked covariance); of the plan's workspace
+ * the call overwrites only what every avz_mvdr_batch call rebuilds (the covariance
+ * partials), so it may sit between two such calls on the same plan and stream.
+ * A row with len[b] < n_fft is not scanned: its n_angles values come back NaN (unlike
+ * avz_stft and avz_mask_features, which leave such a row unwritten). Degenerate maps follow
+ * the reference's arithmetic: when every scanned power is 0 (an all-zero mixture, or a band
+ * [f_lo, f_hi] that holds no bin) each value is -inf - (-inf) = NaN, as
+ * debug_srp.py:61-62 gives. */
 int avz_srp_scan(const avz_plan* plan, int batch, const int* len, int max_len,
                  const float* mix, long long mix_stride, long long ch_stride, int n_angles,
                  double angle_lo, double angle_hi, double f_lo, double f_hi, double* power_db,

@@ -2216,7 +2216,9 @@ __global__ void __launch_bounds__(kSrpThreads) avz_srp_kernel(ChainArgs A, SrpAr
   // f_k = rfftfreq(N, 1/fs)[k]; the scanned bins
   const double df = 1.0 / (N * (1.0 / A.fs));
   const double step = (S.n_angles > 1) ? (S.angle_hi - S.angle_lo) / (S.n_angles - 1) : 0.0;
-  double best = -1e300;
+  // -inf, not a finite floor: a map whose powers are all 0 (an all-zero mixture, a band that
+  // holds no bin) comes back as -inf - (-inf) = NaN, as debug_srp.py:61-62 gives
+  double best = -__builtin_inf();
   for (int i = tid; i < S.n_angles; i += kSrpThreads) {
     const double ang = (i == S.n_angles - 1 && S.n_angles > 1) ? S.angle_hi : S.angle_lo + i * step;
     const double th = ang * (M_PI / 180.0);
