@@ -587,6 +587,79 @@ typedef struct avz_stream_args {
 } avz_stream_args;
 int avz_stream_push(const avz_plan* plan, const avz_stream_args* args, void* hip_stream);
 
+/* ------------------------------------------------------------------ streaming online WPE
+ * The causal form of WPE: recursive-least-squares (RLS) online WPE (Yoshioka et al. 2009;
+ * Caroselli et al. 2017), run hop by hop with the framing and the state rules of
+ * avz_stream_push, whose first stage it is. The algorithm is the contract (DESIGN.md section
+ * 15; avz/dereverb.py wpe_stream_numpy is the fp64 restatement); no bit parity with nara_wpe
+ * is claimed. Per stream, with H = n_fft / 2, x_t the t-th hop pushed since the last reset
+ * (two mics), x_-1 = 0, K = taps, D = delay, n = 2 K and W = K + D + 1; per frame t and bin k
+ * (all F bins, DC and Nyquist included):
+ *  - analysis: Y_t = rfft(w [x_t-1 | x_t]) / sum(w) under the plan's fp32 periodic Hann, the
+ *    frame avz_stream_push forms, rounded to complex64; everything below takes that value,
+ *    promoted to fp64;
+ *  - regressor y~_t in C^n: row 2 tau + m is Y[m, t - D - tau], tau = 0 .. K-1, and 0 where
+ *    that frame index is negative (the row order of avz_wpe_spectral);
+ *  - output z_t = y_t - G_t-1^H y~_t (both mics): the a-priori prediction error;
+ *  - power p_t = (1 / (2 W)) sum_{s = max(0, t-W+1)}^{t} sum_m |Y[m, s]|^2 (fixed divisor);
+ *  - RLS step, where the stream's adapt flag is non-zero: u = Q_t-1 y~_t,
+ *    den = forget max(p_t, power_floor) + Re(y~_t^H u), k = u / den, G_t = G_t-1 + k z_t^H,
+ *    Q_t = (Q_t-1 - k u^H) / forget, taken as a product with 1 / forget rounded once. Q_t is
+ *    kept exactly Hermitian: the lower triangle is computed and mirrored, the diagonal is
+ *    real. With adapt = 0, G and Q stay and z_t is computed with the frozen filter;
+ *  - start: G_-1 = 0, Q_-1 = q_init I. All state arithmetic is fp64;
+ *  - synthesis per mic, as avz_stream_push: g_t = irfft(z_t) sum(w) w, output hop t =
+ *    (g_t-1[H:] + g_t[:H]) / (w^2[j] + w^2[j + H]) for t >= 1 and zeros for t = 0: one hop of
+ *    algorithmic latency; one extra hop of zeros drains the tail.
+ * The plan supplies n_fft, the window and max_batch; its mask, beamformer and normalisation
+ * settings are ignored.
+ *
+ * The state is one caller-owned device buffer of avz_wpe_stream_state_bytes(plan, streams,
+ * taps, delay) bytes, 256-byte aligned; its layout is private. Per stream: a header (frame
+ * count, taps, delay, n_fft), the previous hop of both mics, both synthesis tails, a complex64
+ * ring of the W most recent frames plus the 8 of a call's current round, the round's Z, and in
+ * fp64 G [F][n][2] and the lower triangle of Q [F][n (n + 1) / 2]: per bin
+ * 16 (K + D + 17) + 64 K + 16 K (2 K + 1) bytes, i.e. 4480 B at K = 10, D = 3 and 10048 B at
+ * K = 16, D = 3; a stream takes 1.15 MB (n_fft 512) or 2.30 MB (1024) at K = 10 and 2.58 /
+ * 5.16 MB at K = 16. No call allocates device memory.
+ *  avz_wpe_stream_reset  starts the selected streams (select[s] != 0; NULL = all): zero
+ *                        history, G = 0, Q = q_init I. A new buffer must be reset first. taps
+ *                        and delay are fixed here: they are recorded in each stream's header
+ *                        and, on the host, against the buffer's address.
+ *  avz_wpe_stream_push   `hops` >= 1 new hops per stream; out gets the same number of samples
+ *                        per mic. A push whose taps or delay differ from those the buffer was
+ *                        last reset with at this address (or on a buffer never reset in this
+ *                        process) returns AVZ_ERR_ARG; the kernels also skip a stream whose
+ *                        header differs.
+ * Checks, all on the host before any HIP call: a NULL plan, args, mix, out or state, taps
+ * outside 1 .. 16, delay outside 1 .. 8, forget outside (0, 1], power_floor <= 0, q_init <= 0
+ * or hops < 1: AVZ_ERR_ARG; streams outside 1 .. max_batch, ch_stride or out_ch_stride <
+ * hops * hop, (streams > 1) mix_stride < ch_stride + hops * hop or out_stride < out_ch_stride
+ * + hops * hop, or state_bytes too small: AVZ_ERR_SHAPE; state not 256-byte aligned, out not
+ * 16-byte aligned or out_stride / out_ch_stride not a multiple of 4: AVZ_ERR_ALIGN.
+ * Guarantees, as avz_stream_push: a stream's outputs and whole final state are bit-identical
+ * however its hops are grouped into calls, whatever its index and whatever the other streams
+ * hold; a NaN in one stream never reaches another. Calls on one state buffer must be
+ * stream-ordered. out [streams][2][hops*hop] can be pushed straight into avz_stream_push as
+ * its mix (two hops of latency in all). */
+long long avz_wpe_stream_state_bytes(const avz_plan* plan, int streams, int taps, int delay);
+int avz_wpe_stream_reset(const avz_plan* plan, void* state, long long state_bytes, int streams,
+                         int taps, int delay, double q_init,
+                         const int* select /* device [streams] or NULL = all */,
+                         void* hip_stream);
+typedef struct avz_wpe_stream_args {
+  int streams, hops, taps, delay;
+  double forget, power_floor;
+  const int* active;            /* device [streams] or NULL; 0 = state and out rows untouched */
+  const int* adapt;             /* device [streams] or NULL = all adapt */
+  const float* mix; long long mix_stride, ch_stride;        /* [streams][2][hops*hop] */
+  float* out;       long long out_stride, out_ch_stride;    /* [streams][2][hops*hop] */
+  float* Y_out; float* Z_out;   /* optional debug, complex64 [streams][2][F][hops] contiguous */
+  double* G_out;                /* optional, complex128 [streams][F][n][2] after the last frame */
+  void* state; long long state_bytes;
+} avz_wpe_stream_args;
+int avz_wpe_stream_push(const avz_plan* plan, const avz_wpe_stream_args* args, void* hip_stream);
+
 const char* avz_strerror(int code);
 /* Last HIP error string recorded by the library on this thread (diagnostics). */
 const char* avz_last_hip_error(void);

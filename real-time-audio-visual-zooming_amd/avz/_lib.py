@@ -48,6 +48,7 @@ EXPORTED = [
     "avz_stoi_workspace_bytes", "avz_stoi_batch",
     "avz_mask_training_batch",
     "avz_stream_state_bytes", "avz_stream_reset", "avz_stream_steer", "avz_stream_push",
+    "avz_wpe_stream_state_bytes", "avz_wpe_stream_reset", "avz_wpe_stream_push",
 ]
 
 
@@ -126,6 +127,18 @@ class AvzStreamArgs(ct.Structure):
         ("mask_stride_f", ct.c_longlong), ("mask_stride_t", ct.c_longlong),
         ("out", ct.c_void_p), ("out_stride", ct.c_longlong),
         ("w_out", ct.c_void_p), ("cov_out", ct.c_void_p), ("mask_out", ct.c_void_p),
+        ("state", ct.c_void_p), ("state_bytes", ct.c_longlong),
+    ]
+
+
+class AvzWpeStreamArgs(ct.Structure):
+    _fields_ = [
+        ("streams", ct.c_int), ("hops", ct.c_int), ("taps", ct.c_int), ("delay", ct.c_int),
+        ("forget", ct.c_double), ("power_floor", ct.c_double),
+        ("active", ct.c_void_p), ("adapt", ct.c_void_p),
+        ("mix", ct.c_void_p), ("mix_stride", ct.c_longlong), ("ch_stride", ct.c_longlong),
+        ("out", ct.c_void_p), ("out_stride", ct.c_longlong), ("out_ch_stride", ct.c_longlong),
+        ("Y_out", ct.c_void_p), ("Z_out", ct.c_void_p), ("G_out", ct.c_void_p),
         ("state", ct.c_void_p), ("state_bytes", ct.c_longlong),
     ]
 
@@ -241,6 +254,18 @@ def _load():
     lib.avz_stream_check_push.argtypes = [CP, SA]
     for name in ("avz_stream_reset", "avz_stream_steer", "avz_stream_push",
                  "avz_stream_check_state", "avz_stream_check_push"):
+        getattr(lib, name).restype = ct.c_int
+    WA = ct.POINTER(AvzWpeStreamArgs)
+    lib.avz_wpe_stream_state_bytes.argtypes = [P, I, I, I]
+    lib.avz_wpe_stream_state_bytes.restype = LL
+    lib.avz_wpe_stream_reset.argtypes = [P, P, LL, I, I, I, D, P, P]
+    lib.avz_wpe_stream_push.argtypes = [P, WA, P]
+    lib.avz_wpe_stream_check_state_bytes.argtypes = [CP, I, I, I]
+    lib.avz_wpe_stream_check_state_bytes.restype = LL
+    lib.avz_wpe_stream_check_reset.argtypes = [CP, P, LL, I, I, I, D]
+    lib.avz_wpe_stream_check_push.argtypes = [CP, WA]
+    for name in ("avz_wpe_stream_reset", "avz_wpe_stream_push", "avz_wpe_stream_check_reset",
+                 "avz_wpe_stream_check_push"):
         getattr(lib, name).restype = ct.c_int
     lib.avz_stoi_taps.argtypes = [DP]
     lib.avz_stoi_taps.restype = ct.c_int

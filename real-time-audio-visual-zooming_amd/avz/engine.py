@@ -548,6 +548,58 @@ def stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out: tor
     return out
 
 
+# ------------------------------------------------------------------ streaming online WPE
+# Thin wrappers over avz_wpe_stream_* (include/avz.h); avz/dereverb.py StreamingWPE owns the
+# state buffer and is the interface to use.
+def wpe_stream_state_bytes(plan: MVDRPlan, streams: int, taps: int = 10, delay: int = 3) -> int:
+    return check(lib.avz_wpe_stream_state_bytes(plan._h, int(streams), int(taps), int(delay)),
+                 "avz_wpe_stream_state_bytes")
+
+
+def wpe_stream_reset(plan: MVDRPlan, state: torch.Tensor, streams: int, taps: int = 10,
+                     delay: int = 3, q_init: float = 1.0, select=None, stream=None):
+    """Start the selected streams (select: int32 [streams] device tensor, None = all): zero
+    history, G = 0, Q = q_init I; fixes the buffer's taps and delay."""
+    check(lib.avz_wpe_stream_reset(plan._h, _ptr(state), state.numel(), int(streams), int(taps),
+                                   int(delay), float(q_init), _ptr(select),
+                                   _stream_handle(stream)), "avz_wpe_stream_reset")
+
+
+def wpe_stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out: torch.Tensor, *,
+                    taps: int = 10, delay: int = 3, forget: float = 0.99,
+                    power_floor: float = 1e-9, active=None, adapt=None, Y_out=None, Z_out=None,
+                    G_out=None, stream=None):
+    """One avz_wpe_stream_push: mix [streams, 2, hops * hop] -> out of the same shape (float32
+    device tensors, samples contiguous). active / adapt int32 [streams]; Y_out / Z_out
+    complex64 [streams, 2, F, hops] and G_out complex128 [streams, F, 2 taps, 2], contiguous."""
+    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or \
+            mix.stride(2) != 1 or not mix.is_cuda:
+        raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
+    streams, _, n = mix.shape
+    if n == 0 or n % plan.hop:
+        raise ValueError("mix must hold a whole number (>= 1) of hops")
+    hops = n // plan.hop
+    if out.dtype != torch.float32 or tuple(out.shape) != (streams, 2, n) or out.stride(2) != 1:
+        raise ValueError("out must be float32 [streams, 2, hops * hop]")
+    a = _lib.AvzWpeStreamArgs()
+    a.streams, a.hops, a.taps, a.delay = streams, hops, int(taps), int(delay)
+    a.forget, a.power_floor = float(forget), float(power_floor)
+    a.active, a.adapt = _ptr(active), _ptr(adapt)
+    a.mix, a.mix_stride, a.ch_stride = _ptr(mix), mix.stride(0), mix.stride(1)
+    a.out, a.out_stride, a.out_ch_stride = _ptr(out), out.stride(0), out.stride(1)
+    for name, t, shape, dt in (("Y_out", Y_out, (streams, 2, plan.F, hops), torch.complex64),
+                               ("Z_out", Z_out, (streams, 2, plan.F, hops), torch.complex64),
+                               ("G_out", G_out, (streams, plan.F, 2 * int(taps), 2),
+                                torch.complex128)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}")
+    a.Y_out, a.Z_out, a.G_out = _ptr(Y_out), _ptr(Z_out), _ptr(G_out)
+    a.state, a.state_bytes = _ptr(state), state.numel()
+    check(lib.avz_wpe_stream_push(plan._h, ct.byref(a), _stream_handle(stream)),
+          "avz_wpe_stream_push")
+    return out
+
+
 def srp_scan(plan: MVDRPlan, mix: torch.Tensor, lengths=None, max_len=None, n_angles=181,
              angle_lo=0.0, angle_hi=180.0, f_lo=200.0, f_hi=4000.0, stream=None):
     """scripts/debug_srp.py:46-62 for a [B, 2, S] batch -> power map [B, n_angles] in dB

@@ -5,10 +5,12 @@
 #include <cmath>
 #include <complex>
 #include <limits>
+#include <mutex>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/avz.h"
@@ -1411,6 +1413,153 @@ extern "C" int avz_stream_push(const avz_plan* p, const avz_stream_args* a, void
   s.state = static_cast<unsigned char*>(a->state);
   s.state_stride = avz::StreamLayout(c.n_fft).stride;
   rc = avz_launch_stream_push(c.n_fft, c.mask_mode, &s, &k, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+// ------------------------------------------------------------------ streaming online WPE
+// As the streaming beamformer's: every check runs on the host before any HIP call, and the
+// avz_wpe_stream_check_* forms take the configuration itself (tests without a device).
+static int wpe_stream_param_check(int taps, int delay) {
+  if (taps < 1 || taps > 16 || delay < 1 || delay > 8) return AVZ_ERR_ARG;
+  return AVZ_OK;
+}
+
+extern "C" long long avz_wpe_stream_check_state_bytes(const avz_config* c, int streams, int taps,
+                                                      int delay) {
+  if (!c) return AVZ_ERR_ARG;
+  const int rc = wpe_stream_param_check(taps, delay);
+  if (rc != AVZ_OK) return rc;
+  if (streams < 1 || streams > c->max_batch) return AVZ_ERR_SHAPE;
+  return avz::WpeStreamLayout(c->n_fft, taps, delay).stride * streams;
+}
+
+static int wpe_stream_state_check(const avz_config& c, const void* state, long long state_bytes,
+                                  int streams, int taps, int delay) {
+  if (!state) return AVZ_ERR_ARG;
+  if (streams < 1 || streams > c.max_batch) return AVZ_ERR_SHAPE;
+  if (state_bytes < avz::WpeStreamLayout(c.n_fft, taps, delay).stride * streams)
+    return AVZ_ERR_SHAPE;
+  if (misaligned(state, 256)) return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+extern "C" int avz_wpe_stream_check_reset(const avz_config* c, const void* state,
+                                          long long state_bytes, int streams, int taps,
+                                          int delay, double q_init) {
+  if (!c) return AVZ_ERR_ARG;
+  const int rc = wpe_stream_param_check(taps, delay);
+  if (rc != AVZ_OK) return rc;
+  if (!(q_init > 0.0) || !std::isfinite(q_init)) return AVZ_ERR_ARG;
+  return wpe_stream_state_check(*c, state, state_bytes, streams, taps, delay);
+}
+
+extern "C" int avz_wpe_stream_check_push(const avz_config* cfg, const avz_wpe_stream_args* a) {
+  if (!cfg || !a) return AVZ_ERR_ARG;
+  const avz_config& c = *cfg;
+  if (!a->mix || !a->out || !a->state) return AVZ_ERR_ARG;
+  int rc = wpe_stream_param_check(a->taps, a->delay);
+  if (rc != AVZ_OK) return rc;
+  if (!(a->forget > 0.0 && a->forget <= 1.0)) return AVZ_ERR_ARG;  // NaN included
+  if (!(a->power_floor > 0.0) || !std::isfinite(a->power_floor)) return AVZ_ERR_ARG;
+  if (a->hops < 1) return AVZ_ERR_ARG;
+  if (a->streams < 1 || a->streams > c.max_batch) return AVZ_ERR_SHAPE;
+  const long long row = (long long)a->hops * c.hop;
+  if (row > (1LL << 30)) return AVZ_ERR_SHAPE;
+  if (a->ch_stride < row || a->out_ch_stride < row) return AVZ_ERR_SHAPE;
+  if (a->streams > 1 &&
+      (a->mix_stride < a->ch_stride + row || a->out_stride < a->out_ch_stride + row))
+    return AVZ_ERR_SHAPE;
+  rc = wpe_stream_state_check(c, a->state, a->state_bytes, a->streams, a->taps, a->delay);
+  if (rc != AVZ_OK) return rc;
+  if (misaligned(a->out, 16) || (a->out_stride & 3) || (a->out_ch_stride & 3))
+    return AVZ_ERR_ALIGN;
+  if (misaligned(a->mix, 4) || misaligned(a->Y_out, 8) || misaligned(a->Z_out, 8) ||
+      misaligned(a->G_out, 16))
+    return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+// taps, delay and n_fft of every state buffer reset in this process, by address: what lets a
+// push be refused on the host, the device header unread.
+namespace {
+struct WpeStreamRecord {
+  int taps, delay, n_fft;
+};
+std::mutex g_wpe_stream_mu;
+std::unordered_map<const void*, WpeStreamRecord> g_wpe_stream_rec;
+}  // namespace
+
+extern "C" long long avz_wpe_stream_state_bytes(const avz_plan* p, int streams, int taps,
+                                                int delay) {
+  if (!p) return AVZ_ERR_ARG;
+  return avz_wpe_stream_check_state_bytes(&p->cfg, streams, taps, delay);
+}
+
+extern "C" int avz_wpe_stream_reset(const avz_plan* p, void* state, long long state_bytes,
+                                    int streams, int taps, int delay, double q_init,
+                                    const int* select, void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = avz_wpe_stream_check_reset(&p->cfg, state, state_bytes, streams, taps, delay, q_init);
+  if (rc != AVZ_OK) return rc;
+  const WpeStreamRecord now{taps, delay, p->cfg.n_fft};
+  {
+    // a partial reset may not change what the other streams of the buffer were laid out for
+    std::lock_guard<std::mutex> lock(g_wpe_stream_mu);
+    auto it = g_wpe_stream_rec.find(state);
+    if (select && (it == g_wpe_stream_rec.end() || it->second.taps != taps ||
+                   it->second.delay != delay || it->second.n_fft != now.n_fft))
+      return AVZ_ERR_ARG;
+    g_wpe_stream_rec[state] = now;
+  }
+  avz::WpeStreamArgs s{};
+  s.streams = streams;
+  s.taps = taps;
+  s.delay = delay;
+  s.q_init = q_init;
+  s.state = static_cast<unsigned char*>(state);
+  s.state_stride = avz::WpeStreamLayout(p->cfg.n_fft, taps, delay).stride;
+  s.select = select;
+  rc = avz_launch_wpe_stream_reset(p->cfg.n_fft, &s, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+extern "C" int avz_wpe_stream_push(const avz_plan* p, const avz_wpe_stream_args* a,
+                                   void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = avz_wpe_stream_check_push(&p->cfg, a);
+  if (rc != AVZ_OK) return rc;
+  const avz_config& c = p->cfg;
+  {
+    std::lock_guard<std::mutex> lock(g_wpe_stream_mu);
+    auto it = g_wpe_stream_rec.find(a->state);
+    if (it == g_wpe_stream_rec.end() || it->second.taps != a->taps ||
+        it->second.delay != a->delay || it->second.n_fft != c.n_fft)
+      return AVZ_ERR_ARG;
+  }
+  avz::WpeStreamArgs s{};
+  s.streams = a->streams;
+  s.hops = a->hops;
+  s.taps = a->taps;
+  s.delay = a->delay;
+  s.forget = a->forget;
+  s.inv_forget = 1.0 / a->forget;
+  s.power_floor = a->power_floor;
+  s.active = a->active;
+  s.adapt = a->adapt;
+  s.mix = a->mix;
+  s.mix_stride = a->mix_stride;
+  s.ch_stride = a->ch_stride;
+  s.out = a->out;
+  s.out_stride = a->out_stride;
+  s.out_ch_stride = a->out_ch_stride;
+  s.Y_out = a->Y_out;
+  s.Z_out = a->Z_out;
+  s.G_out = a->G_out;
+  s.state = static_cast<unsigned char*>(a->state);
+  s.state_stride = avz::WpeStreamLayout(c.n_fft, a->taps, a->delay).stride;
+  rc = avz_launch_wpe_stream_push(c.n_fft, &s, p->xwin, stream);
   if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
   return rc;
 }

@@ -284,6 +284,57 @@ struct StreamLayout {
   }
 };
 
+// Streaming online WPE (avz_wpe_stream_push / _reset, avz_wpe_stream.hip).
+struct WpeStreamArgs {
+  int streams, hops, taps, delay;
+  double forget, inv_forget, power_floor, q_init;
+  const int* active;          // [streams] or null: 0 = the stream is skipped
+  const int* adapt;           // [streams] or null: 0 = G and Q freeze
+  const float* mix;           // [streams][2][hops * H] planar
+  long long mix_stride, ch_stride;
+  float* out;                 // [streams][2][hops * H]
+  long long out_stride, out_ch_stride;
+  float* Y_out;               // complex64 [streams][2][F][hops] or null
+  float* Z_out;
+  double* G_out;              // complex128 [streams][F][n][2] or null
+  unsigned char* state;       // [streams][state_stride bytes]
+  long long state_stride;
+  const int* select;          // reset: [streams] or null = all
+  int j0, nf;                 // the round: hops [j0, j0 + nf) of the call, nf <= 8
+};
+
+constexpr int kWpeStreamRound = 8;  // frames per round: the lane groups of a 256-thread block
+
+// One stream's state block for n_fft = N (H = N / 2, F = H + 1), K taps, delay D, n = 2 K,
+// W = K + D + 1, R = W + 8 ring slots:
+//   header 256 B: frame count (u64), taps, delay, n_fft (i32)
+//   prev  [2][H] f32      the previous hop of both mics
+//   tail  [2][H] f32      g[H:] of the last frame, both mics
+//   ring  [F][R][2] c64   frame t of bin k at slot t mod R (bin-major)
+//   zr    [8][F][2] c64   Z of frame t at slot t mod 8: the round's hand-over to the synthesis
+//   G     [F][n][2] c128
+//   Q     [F][n (n + 1) / 2] c128   lower triangle, row-major: Q[i][j], j <= i
+// every section 256-byte aligned, the block rounded up to 256 bytes.
+struct WpeStreamLayout {
+  long long prev_off = 0, tail_off = 0, ring_off = 0, zr_off = 0, g_off = 0, q_off = 0, stride = 0;
+  int n = 0, W = 0, R = 0, tri = 0;
+  constexpr WpeStreamLayout(int n_fft, int taps, int delay) {  // constexpr: host and device
+    const long long H = n_fft / 2, F = H + 1;
+    auto up = [](long long v) { return (v + 255) & ~255LL; };
+    n = 2 * taps;
+    W = taps + delay + 1;
+    R = W + kWpeStreamRound;
+    tri = n * (n + 1) / 2;
+    prev_off = 256;
+    tail_off = up(prev_off + 2 * H * 4);
+    ring_off = up(tail_off + 2 * H * 4);
+    zr_off = up(ring_off + F * R * 16);
+    g_off = up(zr_off + kWpeStreamRound * F * 16);
+    q_off = up(g_off + F * n * 32);
+    stride = up(q_off + F * tri * 16);
+  }
+};
+
 struct SrpArgs {
   int n_angles;
   double angle_lo, angle_hi;  // np.linspace(angle_lo, angle_hi, n_angles)
@@ -404,4 +455,7 @@ int avz_launch_stream_reset(int n_fft, const avz::StreamArgs* s, const double* p
                             void* stream);
 int avz_launch_stream_steer(int n_fft, const avz::StreamArgs* s, double mic_d, double c_sound,
                             double fs, void* stream);
+int avz_launch_wpe_stream_push(int n_fft, const avz::WpeStreamArgs* a, const float* xwin,
+                               void* stream);
+int avz_launch_wpe_stream_reset(int n_fft, const avz::WpeStreamArgs* a, void* stream);
 }
