@@ -1,6 +1,7 @@
-// avz_chunked.hip — launchers of the chunk-parallel chain and the per-utterance synthesis
-// kernels (kernels: avz_chunked_k.hpp; the analysis and chunk-synthesis instantiations are
-// compiled in their own units, avz_chunked_inst.hpp).
+// avz_chunked.hip — launchers of the chunk-parallel chain (kernels: avz_chunked_k.hpp). Every
+// chain kernel is instantiated explicitly from the lists of avz_chunked_inst.hpp (here, or
+// the analysis and chunk-synthesis ones in their own units with SPLIT=1), so the launchers
+// are host code only: which of them names a kernel first does not move it in the code object.
 #include "avz_chunked_k.hpp"
 #include "avz_chunked_inst.hpp"
 
@@ -15,9 +16,11 @@ AVZ_ANALYSIS_INST(512)
 AVZ_SYN_INST(1024)
 AVZ_SYN_INST(512)
 #undef AVZ_INST
-// the per-utterance synthesis kernels: with the launchers in either build
+// the per-utterance synthesis kernels and the solve, SRP and finalize kernels: with the
+// launchers in either build
 #define AVZ_INST template
 AVZ_UTT_INST
+AVZ_CHAIN_INST
 #undef AVZ_INST
 }  // namespace avz
 
@@ -25,7 +28,48 @@ using namespace avz;
 
 extern "C" int avz_chunk_frames(void) { return kChunk; }
 
-static int resident_cus();
+// Compute units of the current device (cached per device id; thread-safe).
+static int resident_cus() {
+  static std::atomic<int> cache[64];
+  int dev = 0, v = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 256;
+  if (dev < 64 && cache[dev].load(std::memory_order_relaxed) > 0)
+    return cache[dev].load(std::memory_order_relaxed);
+  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+    v = 256;
+  if (dev < 64) cache[dev].store(v, std::memory_order_relaxed);
+  return v;
+}
+
+// Kernel K with its dynamic-LDS attribute set on the current device (lds_ready), or null.
+using ChainKernel = void (*)(ChainArgs);
+template <auto K>
+static ChainKernel ready_kernel(int lds) {
+  return lds_ready<K>(lds) ? K : nullptr;
+}
+
+// The chain's transform sizes and mask modes as template arguments: f(N) / f(N, MASK) with
+// integral constants; -4 for a size or a mode the chain has no kernels for.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <class Fn>
+static int for_n_fft(int n_fft, Fn&& f) {
+  if (n_fft == 1024) return f(int_c<1024>{});
+  if (n_fft == 512) return f(int_c<512>{});
+  return -4;
+}
+template <class Fn>
+static int for_n_fft_mask(int n_fft, int mask_mode, Fn&& f) {
+  return for_n_fft(n_fft, [&](auto n) {
+    switch (mask_mode) {
+      case MASK_IBM: return f(n, int_c<MASK_IBM>{});
+      case MASK_IPD: return f(n, int_c<MASK_IPD>{});
+      case MASK_EXTERNAL: return f(n, int_c<MASK_EXTERNAL>{});
+      case MASK_ONES: return f(n, int_c<MASK_ONES>{});
+    }
+    return -4;
+  });
+}
 
 // The per-utterance kernel covers the IBM-target and unfiltered post-filters (the headline
 // and the IPD configuration); the IRM and external-mask gains, read per (bin, frame) from
@@ -101,13 +145,25 @@ static int solve_blocks(const ChainArgs* a, bool lanes) {
   return (int)(((long long)a->batch * (N / 2 + 1) + per - 1) / per);
 }
 
+// The synthesis launch of the chain and of the stage exports (persistent grid).
+template <int N, int PF, bool SPEC = false>
+static int launch_synthesis(const ChainArgs* a, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const int nch = (a->max_frames + kChunk - 1) / kChunk;
+  constexpr int lds = SGeo<N, kSynR<N, PF>>::LDS_BYTES;
+  const auto kern = ready_kernel<avz_synthesis_kernel<N, PF, SPEC>>(lds);
+  if (!kern) return -3;
+  const int n_items = nch * a->batch;
+  if (n_items == 0) return 0;
+  const dim3 sgrid((unsigned)std::min(n_items, KCfg<N>::SYN_BLOCKS_PER_CU * resident_cus()));
+  hipExtLaunchKernelGGL(kern, sgrid, dim3(kCThreads), lds, st, e0, e1, 0, *a);
+  return 0;
+}
+
 // Synthesis + output normalisation of the chain and of the stage exports: the per-utterance
 // kernel (time-domain input, peak normalisation; finalize events record an empty span unless
 // the N = 1024 split has pieces, whose solve and finalize launches the solve and finalize
 // events then time), or the persistent chunk grid followed by avz_finalize_kernel. ev: the
 // (start, stop) event pairs of the solve, synthesis and finalize launches (6, may be null).
-template <int N, int PF, bool SPEC = false>
-static int launch_synthesis(const ChainArgs* a, hipStream_t st, hipEvent_t e0, hipEvent_t e1);
 template <int N, int PF, bool SPEC = false>
 static int launch_synth_finalize(const ChainArgs* a0, hipStream_t st, const hipEvent_t* ev,
                                  bool fused_solve = false) {
@@ -127,22 +183,16 @@ static int launch_synth_finalize(const ChainArgs* a0, hipStream_t st, const hipE
       c.s_steps = sp.steps;
       c.s_ipf = sp.ipf ? 1 : 0;
       grid = dim3((unsigned)sp.grid);
-    }
-    if constexpr (N == 1024) {
       constexpr int lds = UttGeo::LDS_BYTES;
       // the general instance for pieces and for split analysis chunks (the whole-rounds one
       // reads only whole-chunk partials)
       const bool pc = c.s_pieces > 0 || c.a_pieces > 1;
-      auto kern = fused_solve ? (pc ? avz_synthesis_utt_kernel<UPF, true, true>
-                                    : avz_synthesis_utt_kernel<UPF, true, false>)
-                              : (pc ? avz_synthesis_utt_kernel<UPF, false, true>
-                                    : avz_synthesis_utt_kernel<UPF, false, false>);
-      const bool ready = fused_solve
-                             ? (pc ? lds_ready<avz_synthesis_utt_kernel<UPF, true, true>>(lds)
-                                   : lds_ready<avz_synthesis_utt_kernel<UPF, true, false>>(lds))
-                             : (pc ? lds_ready<avz_synthesis_utt_kernel<UPF, false, true>>(lds)
-                                   : lds_ready<avz_synthesis_utt_kernel<UPF, false, false>>(lds));
-      if (!ready) return -3;
+      const auto kern =
+          fused_solve ? (pc ? ready_kernel<avz_synthesis_utt_kernel<UPF, true, true>>(lds)
+                            : ready_kernel<avz_synthesis_utt_kernel<UPF, true, false>>(lds))
+                      : (pc ? ready_kernel<avz_synthesis_utt_kernel<UPF, false, true>>(lds)
+                            : ready_kernel<avz_synthesis_utt_kernel<UPF, false, false>>(lds));
+      if (!kern) return -3;
       hipExtLaunchKernelGGL(kern, grid, dim3(kUttThreads), lds, st, e0, e1, 0, *a);
       if (c.s_pieces > 0 && !c.s_ipf) {
         const int T = a->max_frames;
@@ -153,11 +203,9 @@ static int launch_synth_finalize(const ChainArgs* a0, hipStream_t st, const hipE
       }
     } else {
       constexpr int lds = Utt512Geo::LDS_BYTES;
-      auto kern = fused_solve ? avz_synthesis_utt512_kernel<UPF, true>
-                              : avz_synthesis_utt512_kernel<UPF, false>;
-      if (!(fused_solve ? lds_ready<avz_synthesis_utt512_kernel<UPF, true>>(lds)
-                        : lds_ready<avz_synthesis_utt512_kernel<UPF, false>>(lds)))
-        return -3;
+      const auto kern = fused_solve ? ready_kernel<avz_synthesis_utt512_kernel<UPF, true>>(lds)
+                                    : ready_kernel<avz_synthesis_utt512_kernel<UPF, false>>(lds);
+      if (!kern) return -3;
       hipExtLaunchKernelGGL(kern, grid, dim3(kUtt512Threads), lds, st, e0, e1, 0, *a);
     }
     return 0;  // no finalize launch unless pieces: its events stay unrecorded (avz_chain_kernels)
@@ -166,20 +214,6 @@ static int launch_synth_finalize(const ChainArgs* a0, hipStream_t st, const hipE
   const int nch = (a->max_frames + kChunk - 1) / kChunk;
   hipExtLaunchKernelGGL(avz_finalize_kernel<N>, dim3(fin_groups<N>(nch), a->batch), dim3(kCThreads),
                         0, st, e2, e3, 0, *a);
-  return 0;
-}
-
-// The synthesis launch of the chain and of the stage exports (persistent grid).
-template <int N, int PF, bool SPEC>
-static int launch_synthesis(const ChainArgs* a, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
-  const int nch = (a->max_frames + kChunk - 1) / kChunk;
-  constexpr int lds = SGeo<N, kSynR<N, PF>>::LDS_BYTES;
-  if (!lds_ready<avz_synthesis_kernel<N, PF, SPEC>>(lds)) return -3;
-  const int n_items = nch * a->batch;
-  if (n_items == 0) return 0;
-  const dim3 sgrid((unsigned)std::min(n_items, KCfg<N>::SYN_BLOCKS_PER_CU * resident_cus()));
-  hipExtLaunchKernelGGL((avz_synthesis_kernel<N, PF, SPEC>), sgrid, dim3(kCThreads), lds, st, e0,
-                        e1, 0, *a);
   return 0;
 }
 
@@ -197,19 +231,6 @@ extern "C" int avz_debug_set_stamps_chunked(void* dev_ptr) {
   return r;
 }
 #endif
-
-// Compute units of the current device (cached per device id; thread-safe).
-static int resident_cus() {
-  static std::atomic<int> cache[64];
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 256;
-  if (dev < 64 && cache[dev].load(std::memory_order_relaxed) > 0)
-    return cache[dev].load(std::memory_order_relaxed);
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-    v = 256;
-  if (dev < 64) cache[dev].store(v, std::memory_order_relaxed);
-  return v;
-}
 
 // Tail splitting of the analysis grid (analysis_items): with G resident blocks, the
 // floor(n / G) G items of the full rounds run whole and the partial last round's items in
@@ -235,7 +256,6 @@ static int analysis_tail(ChainArgs& c, int n_items, int G, int SA) {
 
 template <int N, int MASK, int PF>
 static int launch_chunked_t(const ChainArgs* a0, hipStream_t st) {
-  auto k3 = avz_finalize_kernel<N>;
   constexpr int lds = CGeo<N>::LDS_BYTES;
   ChainArgs c = *a0;  // this launch's copy (tail splitting parameters)
   const ChainArgs* a = &c;
@@ -245,14 +265,12 @@ static int launch_chunked_t(const ChainArgs* a0, hipStream_t st) {
   constexpr int SA = kChunk / ((MASK == MASK_IBM) ? CGeo<N>::NSLOT / 2 : CGeo<N>::NSLOT);
   const dim3 pgrid((unsigned)analysis_tail(c, n_items, CGeo<N>::BLOCKS * resident_cus(), SA));
   const bool split = c.a_pieces > 1;  // the SPLIT instances only then
-  auto k1 = split ? avz_analysis_kernel<N, MASK, PF == PF_IRM, true>
-                  : avz_analysis_kernel<N, MASK, PF == PF_IRM, false>;
+  const auto k1 = split ? ready_kernel<avz_analysis_kernel<N, MASK, PF == PF_IRM, true>>(lds)
+                        : ready_kernel<avz_analysis_kernel<N, MASK, PF == PF_IRM, false>>(lds);
+  if (!k1) return -3;
   const bool lanes = split && few_solve_threads<N>(a);
-  auto ks = lanes ? avz_solve_lanes_kernel<N>
-                  : (split ? avz_solve_kernel<N, true> : avz_solve_kernel<N, false>);
-  if (!(split ? lds_ready<avz_analysis_kernel<N, MASK, PF == PF_IRM, true>>(lds)
-              : lds_ready<avz_analysis_kernel<N, MASK, PF == PF_IRM, false>>(lds)))
-    return -3;
+  const auto ks = lanes ? avz_solve_lanes_kernel<N>
+                        : (split ? avz_solve_kernel<N, true> : avz_solve_kernel<N, false>);
   const int nsolve = solve_blocks<N>(a, lanes), nfix = solve_blocks<N>(a, false);
   // diagnostic timing: kernel i's (start, stop) events ride on its own dispatch packet
   // (hipExtLaunchKernel), so timing adds no marker packets between the launches
@@ -271,7 +289,6 @@ static int launch_chunked_t(const ChainArgs* a0, hipStream_t st) {
   } else {
     hipExtLaunchKernelGGL(ks, dim3(nsolve), dim3(kSolveThreads), 0, st, evt(2), evt(3), 0, *a);
   }
-  (void)k3;
   const hipEvent_t sev[6] = {evt(2), evt(3), evt(4), evt(5), evt(6), evt(7)};
   if (launch_synth_finalize<N, PF>(a, st, sev, fused) != 0) return -3;
   return hipGetLastError() == hipSuccess ? 0 : -3;
@@ -293,9 +310,9 @@ static int launch_pf(const ChainArgs* a, hipStream_t st) {
 
 template <int N>
 static int launch_srp_t(const ChainArgs* a, const SrpArgs* s, hipStream_t st) {
-  auto k1 = avz_analysis_kernel<N, MASK_ONES, false>;
   constexpr int lds = CGeo<N>::LDS_BYTES;
-  if (!lds_ready<avz_analysis_kernel<N, MASK_ONES, false>>(lds)) return -3;
+  const auto k1 = ready_kernel<avz_analysis_kernel<N, MASK_ONES, false>>(lds);
+  if (!k1) return -3;
   const int nch = (a->max_frames + kChunk - 1) / kChunk;
   if (nch > a->nchunk) return -2;
   const int n_items = nch * a->batch;
@@ -307,9 +324,7 @@ static int launch_srp_t(const ChainArgs* a, const SrpArgs* s, hipStream_t st) {
 
 extern "C" int avz_launch_srp(int n_fft, const ChainArgs* a, const SrpArgs* s, void* stream) {
   if (a->batch <= 0) return 0;
-  if (n_fft == 1024) return launch_srp_t<1024>(a, s, (hipStream_t)stream);
-  if (n_fft == 512) return launch_srp_t<512>(a, s, (hipStream_t)stream);
-  return -4;
+  return for_n_fft(n_fft, [&](auto n) { return launch_srp_t<n()>(a, s, (hipStream_t)stream); });
 }
 
 template <int N>
@@ -324,8 +339,10 @@ static void chain_kernels_t(const ChainArgs* a, bool& utt, bool& fused) {
 }
 extern "C" int avz_chain_kernels(int n_fft, const ChainArgs* a) {
   bool utt = false, fused = false;
-  if (n_fft == 1024) chain_kernels_t<1024>(a, utt, fused);
-  if (n_fft == 512) chain_kernels_t<512>(a, utt, fused);
+  for_n_fft(n_fft, [&](auto n) {
+    chain_kernels_t<n()>(a, utt, fused);
+    return 0;
+  });
   // the N = 1024 per-utterance kernel's pieces below whole rounds bring a finalize launch
   const SynthSplit sp = n_fft == 1024 ? synth_split(a) : SynthSplit{0, 0, 0, 0, false};
   const bool fin = utt && n_fft == 1024 && sp.pieces > 0 && !sp.ipf;
@@ -335,22 +352,8 @@ extern "C" int avz_chain_kernels(int n_fft, const ChainArgs* a) {
 extern "C" int avz_launch_chunked(int n_fft, int mask_mode, const ChainArgs* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (a->batch <= 0) return 0;
-  if (n_fft == 1024) {
-    switch (mask_mode) {
-      case MASK_IBM: return launch_pf<1024, MASK_IBM>(a, st);
-      case MASK_IPD: return launch_pf<1024, MASK_IPD>(a, st);
-      case MASK_EXTERNAL: return launch_pf<1024, MASK_EXTERNAL>(a, st);
-      case MASK_ONES: return launch_pf<1024, MASK_ONES>(a, st);
-    }
-  } else if (n_fft == 512) {
-    switch (mask_mode) {
-      case MASK_IBM: return launch_pf<512, MASK_IBM>(a, st);
-      case MASK_IPD: return launch_pf<512, MASK_IPD>(a, st);
-      case MASK_EXTERNAL: return launch_pf<512, MASK_EXTERNAL>(a, st);
-      case MASK_ONES: return launch_pf<512, MASK_ONES>(a, st);
-    }
-  }
-  return -4;
+  return for_n_fft_mask(n_fft, mask_mode,
+                        [&](auto n, auto m) { return launch_pf<n(), m()>(a, st); });
 }
 
 // ================================ stage exports ================================
@@ -368,9 +371,10 @@ __global__ void __launch_bounds__(256) avz_coef_kernel(ChainArgs A, const float*
 template <int N, int MASK>
 static int launch_cov_t(const ChainArgs* a, hipStream_t st) {
   constexpr int lds = CGeo<N>::LDS_BYTES;
-  if (!lds_ready<avz_analysis_kernel<N, MASK, false, true>>(lds) ||
-      !lds_ready<avz_analysis_kernel<N, MASK, false, false>>(lds))
-    return -3;
+  const auto ka_split = ready_kernel<avz_analysis_kernel<N, MASK, false, true>>(lds);
+  const auto ka_whole =
+      ka_split ? ready_kernel<avz_analysis_kernel<N, MASK, false, false>>(lds) : nullptr;
+  if (!ka_whole) return -3;
   const int nch = (a->max_frames + kChunk - 1) / kChunk;
   if (nch > a->nchunk) return -2;
   const int n_items = nch * a->batch;
@@ -382,8 +386,7 @@ static int launch_cov_t(const ChainArgs* a, hipStream_t st) {
   constexpr int SA = kChunk / ((MASK == MASK_IBM) ? CGeo<N>::NSLOT / 2 : CGeo<N>::NSLOT);
   const int grid = analysis_tail(c, n_items, CGeo<N>::BLOCKS * resident_cus(), SA);
   const bool split = c.a_pieces > 1;
-  auto ka = split ? avz_analysis_kernel<N, MASK, false, true>
-                  : avz_analysis_kernel<N, MASK, false, false>;
+  const auto ka = split ? ka_split : ka_whole;
   const bool lanes = split && few_solve_threads<N>(a);
   auto ks = lanes ? avz_solve_lanes_kernel<N>
                   : (split ? avz_solve_kernel<N, true> : avz_solve_kernel<N, false>);
@@ -395,17 +398,8 @@ static int launch_cov_t(const ChainArgs* a, hipStream_t st) {
 extern "C" int avz_launch_covariance(int n_fft, int mask_mode, const ChainArgs* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (a->batch <= 0) return 0;
-#define AVZ_COV_CASES(NN)                                                   \
-  switch (mask_mode) {                                                      \
-    case MASK_IBM: return launch_cov_t<NN, MASK_IBM>(a, st);                \
-    case MASK_IPD: return launch_cov_t<NN, MASK_IPD>(a, st);                \
-    case MASK_EXTERNAL: return launch_cov_t<NN, MASK_EXTERNAL>(a, st);      \
-    case MASK_ONES: return launch_cov_t<NN, MASK_ONES>(a, st);              \
-  }
-  if (n_fft == 1024) { AVZ_COV_CASES(1024) }
-  if (n_fft == 512) { AVZ_COV_CASES(512) }
-#undef AVZ_COV_CASES
-  return -4;
+  return for_n_fft_mask(n_fft, mask_mode,
+                        [&](auto n, auto m) { return launch_cov_t<n(), m()>(a, st); });
 }
 
 template <int N, int PF, bool SPEC>
@@ -430,17 +424,14 @@ extern "C" int avz_launch_apply_istft(int n_fft, const ChainArgs* a, const float
   const long long n = (long long)a->batch * F;
   hipLaunchKernelGGL(avz_coef_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *a, w, F);
   const bool g = a->ext_mask != nullptr;
-  if (n_fft == 1024)
-    return g ? launch_synth_t<1024, PF_EXT_MUL, false>(a, st) : launch_synth_t<1024, PF_NONE, false>(a, st);
-  if (n_fft == 512)
-    return g ? launch_synth_t<512, PF_EXT_MUL, false>(a, st) : launch_synth_t<512, PF_NONE, false>(a, st);
-  return -4;
+  return for_n_fft(n_fft, [&](auto n) {
+    return g ? launch_synth_t<n(), PF_EXT_MUL, false>(a, st)
+             : launch_synth_t<n(), PF_NONE, false>(a, st);
+  });
 }
 
 extern "C" int avz_launch_istft(int n_fft, const ChainArgs* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (a->batch <= 0) return 0;
-  if (n_fft == 1024) return launch_synth_t<1024, PF_NONE, true>(a, st);
-  if (n_fft == 512) return launch_synth_t<512, PF_NONE, true>(a, st);
-  return -4;
+  return for_n_fft(n_fft, [&](auto n) { return launch_synth_t<n(), PF_NONE, true>(a, st); });
 }

@@ -1,6 +1,6 @@
 // avz_chunked_ana1024.hip — N = 1024 analysis kernels: device code of the chain kernels compiled in parallel with the other units
-// (instantiation list: avz_chunked_inst.hpp; kernels: avz_chunked_k.hpp).
-#include "avz_chunked_k.hpp"
+// (instantiation list: avz_chunked_inst.hpp; kernels: avz_chain_analysis.hpp).
+#include "avz_chain_analysis.hpp"
 #include "avz_chunked_inst.hpp"
 
 namespace avz {

@@ -28,6 +28,23 @@
   AVZ_INST __global__ void avz_synthesis_utt512_kernel<PF_NONE, true>(ChainArgs);            \
   AVZ_INST __global__ void avz_synthesis_utt512_kernel<PF_IBM_TARGET, false>(ChainArgs);     \
   AVZ_INST __global__ void avz_synthesis_utt512_kernel<PF_IBM_TARGET, true>(ChainArgs);
+// The kernels the launchers' unit compiles in both build modes besides AVZ_UTT_INST: solve,
+// solve-lanes, solve-fixup, SRP, finalize and finalize-pieces. The list's order is the
+// kernels' order in the code object: kept as the launchers' first uses once gave it, because
+// code placement has measured effects (the Makefile's note: 4 bytes moved the per-utterance
+// synthesis hot loop by 2.5-3 us). No kernel's place depends on which launcher names it first.
+#define AVZ_SOLVE_FIN_INST(N)                                                        \
+  AVZ_INST __global__ void avz_finalize_kernel<N>(ChainArgs);                        \
+  AVZ_INST __global__ void avz_solve_kernel<N, true>(ChainArgs);                     \
+  AVZ_INST __global__ void avz_solve_kernel<N, false>(ChainArgs);                    \
+  AVZ_INST __global__ void avz_solve_lanes_kernel<N>(ChainArgs);                     \
+  AVZ_INST __global__ void avz_solve_fixup_kernel<N>(ChainArgs);
+#define AVZ_CHAIN_INST                                                               \
+  AVZ_INST __global__ void avz_srp_kernel<1024>(ChainArgs, SrpArgs);                 \
+  AVZ_INST __global__ void avz_srp_kernel<512>(ChainArgs, SrpArgs);                  \
+  AVZ_SOLVE_FIN_INST(1024)                                                           \
+  AVZ_INST __global__ void avz_finalize_pieces_kernel<1024>(ChainArgs);              \
+  AVZ_SOLVE_FIN_INST(512)
 #define AVZ_SYN_INST(N)                                                              \
   AVZ_INST __global__ void avz_synthesis_kernel<N, PF_NONE, false>(ChainArgs);       \
   AVZ_INST __global__ void avz_synthesis_kernel<N, PF_NONE, true>(ChainArgs);        \

@@ -1,6 +1,6 @@
 // avz_chunked_syn.hip — chunk-grid synthesis kernels: device code of the chain kernels compiled in parallel with the other units
-// (instantiation list: avz_chunked_inst.hpp; kernels: avz_chunked_k.hpp).
-#include "avz_chunked_k.hpp"
+// (instantiation list: avz_chunked_inst.hpp; kernels: avz_chain_synthesis.hpp).
+#include "avz_chain_synthesis.hpp"
 #include "avz_chunked_inst.hpp"
 
 namespace avz {

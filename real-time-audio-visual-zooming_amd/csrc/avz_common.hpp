@@ -59,8 +59,29 @@ static __device__ unsigned long long* g_stamps;
     if (threadIdx.x == 0 && g_stamps)                                                   \
       g_stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 16 + (i)] = (unsigned long long)(v); \
   } while (0)
+// an interval of the exact path: AVZ_XT_BEGIN(t) reads the clock into t, AVZ_XT_END(i, t) adds
+// the ticks since then to g_stamps[blockIdx.x][i]; AVZ_XT_LAP(i, t) adds them and restarts t
+#define AVZ_XT_BEGIN(t) const unsigned long long t = __builtin_amdgcn_s_memrealtime()
+#define AVZ_XT_END(i, t)                                                                \
+  do {                                                                                  \
+    if (threadIdx.x == 0 && g_stamps)                                                   \
+      g_stamps[blockIdx.x * 16 + (i)] += __builtin_amdgcn_s_memrealtime() - (t);        \
+  } while (0)
+#define AVZ_XT_LAP_BEGIN(t) unsigned long long t = __builtin_amdgcn_s_memrealtime()
+#define AVZ_XT_LAP(i, t)                                                                \
+  do {                                                                                  \
+    if (threadIdx.x == 0 && g_stamps) {                                                 \
+      const unsigned long long now_ = __builtin_amdgcn_s_memrealtime();                 \
+      g_stamps[blockIdx.x * 16 + (i)] += now_ - t;                                      \
+      t = now_;                                                                         \
+    }                                                                                   \
+  } while (0)
 #else
 #define AVZ_XT(i, v) (void)0
+#define AVZ_XT_LAP_BEGIN(t) (void)0
+#define AVZ_XT_LAP(i, t) (void)0
+#define AVZ_XT_BEGIN(t) (void)0
+#define AVZ_XT_END(i, t) (void)0
 #endif
 
 // Unchecked-sign form for a wave whose samples are all at index >= 0: the offset is a

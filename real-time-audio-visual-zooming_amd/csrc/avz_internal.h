@@ -18,10 +18,10 @@ struct PieceState {
 };
 static_assert(sizeof(PieceState) == 16, "one 16-B store resets it");
 
-// Pieces a shared unit of the exact IBM path splits into at most (avz_chunked_k.hpp XPieces).
+// Pieces a shared unit of the exact IBM path splits into at most (avz_chain_exact.hpp XPieces).
 constexpr int kXPieces = 8;
 
-// Level rule of the exact-IBM certificate (avz_chunked_k.hpp ibm_uncertain): the frame
+// Level rule of the exact-IBM certificate (avz_chain_common.hpp ibm_uncertain): the frame
 // energies E for which an fp32 decision may be certified at all, as float bits [lo, lo + span]
 // (positive floats order as their bits, so the kernels test `bits(E) - lo > span`, unsigned:
 // one compare that also sends 0, inf and NaN outside). c is delta per unit sqrt(E): delta =
@@ -155,7 +155,7 @@ struct ChainArgs {
   uint32_t* xunc;             // [units][32 frames][32] reference-bit path: the frame's
                               // uncertain bins (word l bit k: bin l + 32 k), deferred frames only
   uint32_t* xst;              // [units][2] exact-path work sharing: state, arrivals (closed
-                              // between launches; avz_chunked_k.hpp kXOpen)
+                              // between launches; avz_chain_exact.hpp kXOpen)
   float* xres;                // [units][kXPieces][5][F] a shared unit's piece sums
   uint32_t* xhint;            // [units / 32] published units (one bit each)
   long long xst_reset;        // host-only: bytes of xst to zero before the launch (a caller's

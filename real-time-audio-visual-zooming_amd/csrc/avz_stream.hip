@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArg
         uint32_t bits = 0;
         for (int f = 0; f < nf; ++f) {
           const cf* Z = slot_ptr<N>(lds, f);
-          // noise <=> |S_i| > |S_t| <=> Re(Z[k] Z[N - k]) < 0 (avz_chunked_k.hpp ibm_noise)
+          // noise <=> |S_i| > |S_t| <=> Re(Z[k] Z[N - k]) < 0 (avz_chain_common.hpp ibm_noise)
           const cf z = Z[k], zp = Z[(N - k) & (N - 1)];
           bits |= (fmaf(z.x, zp.x, -(z.y * zp.y)) < 0.0f ? 1u : 0u) << f;
         }

@@ -11,7 +11,7 @@
 // read once, no spectrum goes to memory.
 //
 // Label: 1 where |S_t| > |S_i|, decided on this kernel's fp32 transform as the chain's
-// ibm_kappa < 0 tier does (avz_chunked_k.hpp ibm_noise): with Z = S_t + i S_i,
+// ibm_kappa < 0 tier does (avz_chain_common.hpp ibm_noise): with Z = S_t + i S_i,
 // |S_t|^2 - |S_i|^2 = Re(Z[k] Z[N - k]), one fused product difference, label = (that > 0).
 // This is NOT the reference-exact path of avz_ibm_exact.hpp: a decision whose margin is below
 // the fp32 transform's error may differ from numpy's. Two all-zero reference frames give

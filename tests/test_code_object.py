@@ -29,8 +29,10 @@ def kernels():
 
 def test_every_kernel_is_listed(kernels):
     # the chain, the stage exports and the around-the-chain kernels are all in the library
-    for k in ("avz_analysis_kernel", "avz_solve_kernel", "avz_synthesis_kernel",
-              "avz_synthesis_utt_kernel", "avz_synthesis_utt512_kernel", "avz_finalize_kernel", "avz_stft_kernel", "avz_metrics_sums_kernel",
+    for k in ("avz_analysis_kernel", "avz_solve_kernel", "avz_solve_lanes_kernel",
+              "avz_solve_fixup_kernel", "avz_srp_kernel", "avz_synthesis_kernel",
+              "avz_synthesis_utt_kernel", "avz_synthesis_utt512_kernel", "avz_finalize_kernel",
+              "avz_finalize_pieces_kernel", "avz_stft_kernel", "avz_metrics_sums_kernel",
               "avz_spectral_rows_kernel", "scene_ar_kernel"):
         assert any(k in n for n in kernels), k
 

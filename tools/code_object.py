@@ -3,6 +3,7 @@
     python tools/code_object.py resources [lib.so]      per-kernel VGPR / SGPR / scratch
     python tools/code_object.py isa lib.so out.s        disassembly of the gfx950 code object
     python tools/code_object.py diff a.so b.so          kernels whose ISA differs
+    python tools/code_object.py text-diff a.so b.so     .text bytes per code object, resources
 
 The gfx950 code object is unbundled from the library's .hip_fatbin section with the ROCm
 LLVM tools (llvm-objcopy, clang-offload-bundler); resources come from the AMDGPU metadata
@@ -12,6 +13,7 @@ scratch.
 """
 from __future__ import annotations
 
+import hashlib
 import os
 import re
 import subprocess
@@ -86,7 +88,9 @@ def _kernels(lib: str) -> dict[str, str]:
         p = os.path.join(d, "x.s")
         isa(lib, p)
         txt = open(p).read()
-    blocks = re.split(r"\n(?=[0-9a-f]* ?<[^>]+>:\n)", txt)
+    # each code object's header line names its temporary file: not part of the last function
+    txt = re.sub(r"(?m)^\S+:\s+file format \S+\n", "", txt)
+    blocks =re.split(r"\n(?=[0-9a-f]* ?<[^>]+>:\n)", txt)
     out = {}
     for b in blocks:
         m = re.match(r"[0-9a-f]* ?<([^>]+)>:\n", b)
@@ -117,6 +121,39 @@ def diff(a: str, b: str) -> int:
     return changed
 
 
+def _text_and_resources(lib: str) -> tuple[list[bytes], dict[str, dict[str, int]]]:
+    with tempfile.TemporaryDirectory() as d:
+        texts = []
+        for i, co in enumerate(extract(lib, d)):
+            t = os.path.join(d, f"text{i}.bin")
+            subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.text={t}", co,
+                            os.path.join(d, "rest.co")], check=True, capture_output=True)
+            texts.append(open(t, "rb").read())
+    return texts, resources(lib)
+
+
+def text_diff(a: str, b: str) -> int:
+    """Byte comparison of the device instructions: the .text section of each gfx950 code
+    object of a and b, in order, and every kernel's resources(). Returns the mismatches."""
+    (ta, ra), (tb, rb) = _text_and_resources(a), _text_and_resources(b)
+    bad = 0
+    if len(ta) != len(tb):
+        print(f"code objects: {len(ta)} vs {len(tb)}")
+        bad += 1
+    for i, (x, y) in enumerate(zip(ta, tb)):
+        same = x == y
+        bad += 0 if same else 1
+        print(f"code object {i}: .text {len(x)} vs {len(y)} bytes, "
+              f"sha256 {hashlib.sha256(x).hexdigest()[:16]} vs {hashlib.sha256(y).hexdigest()[:16]}: "
+              + ("equal" if same else "DIFFERENT"))
+    names = sorted(set(ra) | set(rb))
+    off = [n for n in names if ra.get(n) != rb.get(n)]
+    for n, d in zip(off, demangle(off) if off else []):
+        print(f"resources differ: {d}: {ra.get(n)} vs {rb.get(n)}")
+    print(f"resources: {len(names) - len(off)} of {len(names)} kernels agree")
+    return bad + len(off)
+
+
 if __name__ == "__main__":
     cmd = sys.argv[1] if len(sys.argv) > 1 else "resources"
     if cmd == "resources":
@@ -129,3 +166,5 @@ if __name__ == "__main__":
         isa(sys.argv[2], sys.argv[3])
     elif cmd == "diff":
         sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
+    elif cmd == "text-diff":
+        sys.exit(1 if text_diff(sys.argv[2], sys.argv[3]) else 0)
