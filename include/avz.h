@@ -441,7 +441,10 @@ int avz_stoi_batch(const avz_stoi_args* args, void* hip_stream);
  * itf[b] = mic-1 interference image / peak. `workspace` holds
  * avz_scene_workspace_bytes(batch, n_src, n) bytes. All arrays device-resident.
  * n even. When n factors into 2, 3 and 5 the delays run as fp64 mixed-radix FFTs
- * (O(n log n)); otherwise as the exact O(n^2) circular convolution. */
+ * (O(n log n)); otherwise as the exact O(n^2) circular convolution (fp32 sums). Both paths
+ * take every even n >= 2 and every delay, |delay| > n samples included; a delay of a whole
+ * number of samples (within 1e-12 in |sin(pi delay)|) is the circular shift by that number,
+ * 0 included (on the O(n^2) path a rotated copy of the source, no sum). */
 long long avz_scene_workspace_bytes(int batch, int n_src, int n);
 int avz_scene_mix(int batch, int n_src, int n, const float* src, const double* angles_deg,
                   const float* noise, double mic_d, double c_sound, double fs, double sir_db,
@@ -495,7 +498,10 @@ int avz_room_rir(const avz_room* room, int batch, int n_src, const double* src_p
  * and shared peak. tgt / itf are the reverberant mic-1 images. The geometry, fs and c come
  * from `room`. n >= 2, odd included. `workspace` holds avz_scene_reverb_workspace_bytes()
  * bytes: 32 (ceil(n_src / 2) + n_src) Lc per utterance, Lc the smallest length 2^a 3^b 5^c
- * >= n + rir_len - 1 (13.3 MB for 4 s, 4 sources, max_order 15 in the reference room). */
+ * >= n + rir_len - 1 (13.3 MB for 4 s, 4 sources, max_order 15 in the reference room), and
+ * 4 batch n_src bytes of flags rounded up to 256. A source that is all zeros stays exactly out
+ * of the scene here and in avz_scene_mix (all-zero interferers: itf = 0 and no SIR gain; an
+ * all-zero target: every output 0), as in synth._mix_images. */
 long long avz_scene_reverb_workspace_bytes(const avz_room* room, int batch, int n_src, int n);
 int avz_scene_reverb_mix(const avz_room* room, int batch, int n_src, int n, const float* src,
                          const double* src_pos, const float* noise, double sir_db,

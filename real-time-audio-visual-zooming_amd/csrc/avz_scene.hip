@@ -321,15 +321,33 @@ __device__ __forceinline__ double scene_tau(const SceneArgs& A, int b, int s, in
   return (A.mic_d / 2) * cos(th - (mic ? M_PI : 0.0)) / A.c_sound;
 }
 
+// live[b][s] = 1 for a source with a non-zero sample (zeroed before the pack kernel; every
+// writer stores the same 1). Splitting a packed transform leaves some 1e-16 of a source in
+// its partner's spectrum: nothing beside a sounding partner, but an all-zero target or
+// all-zero interferers must stay exactly zero (p_i > 0 decides the SIR gain, and a silent
+// scene is divided by a peak of 1e-9), so the products skip the sources that are not live.
+__device__ __forceinline__ void scene_mark_live(int* live, double re, double im, bool has_im) {
+  const int any_re = __syncthreads_or(re != 0.0), any_im = __syncthreads_or(im != 0.0);
+  if (threadIdx.x == 0) {
+    if (any_re) live[0] = 1;
+    if (has_im && any_im) live[1] = 1;
+  }
+}
+
 // Sources packed two per complex signal: z[b][p][m] = src[2p][m] + i src[2p + 1][m].
-__global__ void __launch_bounds__(256) scene_pack_kernel(SceneArgs A, double2* z, long long sb) {
+__global__ void __launch_bounds__(256) scene_pack_kernel(SceneArgs A, double2* z, long long sb,
+                                                         int* live) {
   const int m = blockIdx.x * 256 + threadIdx.x;
-  if (m >= A.n) return;
   const int b = blockIdx.y, p = blockIdx.z;
+  const bool has_im = 2 * p + 1 < A.n_src;
   const float* y = A.src + (long long)b * A.n_src * A.n;
-  const double re = (double)y[(long long)(2 * p) * A.n + m];
-  const double im = (2 * p + 1 < A.n_src) ? (double)y[(long long)(2 * p + 1) * A.n + m] : 0.0;
-  z[(long long)b * sb + (long long)p * A.n + m] = make_double2(re, im);
+  double re = 0.0, im = 0.0;
+  if (m < A.n) {
+    re = (double)y[(long long)(2 * p) * A.n + m];
+    if (has_im) im = (double)y[(long long)(2 * p + 1) * A.n + m];
+    z[(long long)b * sb + (long long)p * A.n + m] = make_double2(re, im);
+  }
+  scene_mark_live(live + (long long)b * A.n_src + 2 * p, re, im, has_im);
 }
 
 // Frequency-domain mixing, thread per bin k <= n/2 of utterance b: source spectra from the
@@ -337,7 +355,8 @@ __global__ void __launch_bounds__(256) scene_pack_kernel(SceneArgs A, double2* z
 // dropped), target / summed-interference images packed two mics per signal, both halves
 // of the Hermitian spectrum written: zo[b][0] = T0 + i T1, zo[b][1] = I0 + i I1.
 __global__ void __launch_bounds__(256) scene_phase_kernel(SceneArgs A, const double2* zf,
-                                                          double2* zo, long long sb) {
+                                                          double2* zo, long long sb,
+                                                          const int* __restrict__ live) {
   const int n = A.n, half = n / 2;
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k > half) return;
@@ -346,6 +365,7 @@ __global__ void __launch_bounds__(256) scene_phase_kernel(SceneArgs A, const dou
   const double f = (double)k * (1.0 / ((double)n * (1.0 / A.fs)));  // np.fft.rfftfreq
   double2 T[2] = {{0, 0}, {0, 0}}, I[2] = {{0, 0}, {0, 0}};
   for (int s = 0; s < A.n_src; ++s) {
+    if (!live[(long long)b * A.n_src + s]) continue;
     const double2* zp = zf + (long long)b * sb + (long long)(s >> 1) * n;
     const double2 z = zp[k], zc = zp[kp];  // Z[k], Z[n - k]
     double2 Y;
@@ -381,7 +401,18 @@ constexpr int kConvM = kConvThreads * kConvOut;      // 2048 outputs per block
 constexpr int kConvJ = 256;                          // inputs per LDS tile
 constexpr int kConvH = kConvM + kConvJ;              // kernel values per tile (2304)
 
-// h tables: one per (utterance, source, mic) signal, h[d] in fp64 -> fp32
+// A delay within kIntDelay of an integer (|sin(pi delta)| below it) is the circular shift by
+// that integer: exact in the rfft model too, whose Nyquist bin exp(-i pi delta) is then real.
+constexpr double kIntDelay = 1e-12;
+__device__ __forceinline__ bool scene_int_shift(double delta, int n, int& shift) {
+  if (!(fabs(sinpi(delta)) < kIntDelay)) return false;
+  shift = (int)(llrint(delta) % n);
+  if (shift < 0) shift += n;
+  return true;
+}
+
+// h tables: one per (utterance, source, mic) signal, h[d] in fp64 -> fp32; an integer delay's
+// table is the shift itself (1 at d = delta mod n): the cotangent form is 0 * inf there.
 __global__ void __launch_bounds__(256) avz_scene_kernel_fill(SceneArgs A) {
   const long long n = A.n;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -391,7 +422,20 @@ __global__ void __launch_bounds__(256) avz_scene_kernel_fill(SceneArgs A) {
   const int d = (int)(idx % n);
   const int mic = sig & 1, s = (sig >> 1) % A.n_src, b = (sig >> 1) / A.n_src;
   const double delta = scene_tau(A, b, s, mic) * A.fs;
-  const double x = ((double)d - delta) / (double)n;
+  int shift;
+  if (scene_int_shift(delta, A.n, shift)) {
+    A.hk[idx] = (d == shift) ? 1.0f : 0.0f;
+    return;
+  }
+  // cot(pi (d - delta) / n) has period n in d: with delta = r + f, r = rint(delta), take
+  // k = (d - r) mod n in [-n/2, n/2) and x = (k - f) / n. (d - delta) / n as it stands loses
+  // f where d - delta is near n: at delta = -2 - 1e-9 and n = 2306 the tap of weight 1 was
+  // off by 5e-4, and nearer the integer the quotient rounded to 1 and the tap to infinity.
+  const double r = rint(delta), f = delta - r;
+  long long k = ((long long)d - (long long)r) % n;
+  if (k < 0) k += n;
+  if (2 * k >= n) k -= n;
+  const double x = ((double)k - f) / (double)n;
   double sn, cs;
   sincospi(x, &sn, &cs);
   const double sd = sinpi(delta);
@@ -413,26 +457,30 @@ __global__ void __launch_bounds__(kConvThreads) avz_scene_conv_kernel(SceneArgs 
   float* img = A.img + (long long)sig * n;
   const int M0 = blockIdx.x * kConvM;
   const int tid = threadIdx.x;
-  // broadside (sin(pi delta) ~ 0): the phase shift is 1 to within fp64 rounding
-  if (fabs(sinpi(scene_tau(A, b, s, mic) * A.fs)) < 1e-12) {
-    for (int m = M0 + tid; m < min(M0 + kConvM, n); m += kConvThreads) img[m] = y[m];
+  // integer delay (0 for the broadside target): a copy, rotated by the delay
+  int shift;
+  if (scene_int_shift(scene_tau(A, b, s, mic) * A.fs, n, shift)) {
+    for (int m = M0 + tid; m < min(M0 + kConvM, n); m += kConvThreads)
+      img[m] = y[m >= shift ? m - shift : m - shift + n];
     return;
   }
   const float* h = A.hk + (long long)sig * n;
   float acc[kConvOut];
 #pragma unroll
   for (int r = 0; r < kConvOut; ++r) acc[r] = 0.0f;
+  const int hstep = kConvThreads % n;
   for (int j0 = 0; j0 < n; j0 += kConvJ) {
     __syncthreads();
     y_t[tid] = (j0 + tid < n) ? y[j0 + tid] : 0.0f;
-    // h_t[i] = h[(M0 - j0 - 255 + i) mod n]
+    // h_t[i] = h[(M0 - j0 - 255 + i) mod n]: a true modulo for every n >= 2 (n may be far
+    // below the 2304-entry window), stepped by 256 mod n so that no index ever reaches n
     int base = (M0 - j0 - (kConvJ - 1)) % n;
     if (base < 0) base += n;
+    int d = (base + tid) % n;
     for (int i = tid; i < kConvH; i += kConvThreads) {
-      int d = base + i;
-      if (d >= n) d -= n;
-      if (d >= n) d -= n;
       h_t[i] = h[d];
+      d += hstep;
+      if (d >= n) d -= n;
     }
     __syncthreads();
 #pragma unroll 2
@@ -673,17 +721,18 @@ __global__ void __launch_bounds__(64) avz_room_rir_kernel(RoomArgs R, int n_src,
 
 // Sources packed two per complex signal and zero padded to the convolution length Lc.
 __global__ void __launch_bounds__(256) room_pack_kernel(SceneArgs A, double2* z, long long sb,
-                                                        int Lc) {
+                                                        int Lc, int* live) {
   const int m = blockIdx.x * 256 + threadIdx.x;
-  if (m >= Lc) return;
   const int b = blockIdx.y, p = blockIdx.z;
+  const bool has_im = 2 * p + 1 < A.n_src;
   const float* y = A.src + (long long)b * A.n_src * A.n;
   double re = 0.0, im = 0.0;
   if (m < A.n) {
     re = (double)y[(long long)(2 * p) * A.n + m];
-    if (2 * p + 1 < A.n_src) im = (double)y[(long long)(2 * p + 1) * A.n + m];
+    if (has_im) im = (double)y[(long long)(2 * p + 1) * A.n + m];
   }
-  z[(long long)b * sb + (long long)p * Lc + m] = make_double2(re, im);
+  if (m < Lc) z[(long long)b * sb + (long long)p * Lc + m] = make_double2(re, im);
+  scene_mark_live(live + (long long)b * A.n_src + 2 * p, re, im, has_im);
 }
 
 // Zero padding of the packed RIR signals h0 + i h1 (signals P .. P + n_src - 1).
@@ -698,7 +747,8 @@ __global__ void __launch_bounds__(256) room_pad_kernel(double2* z, long long sb,
 // transform) times the spectrum of h0 + i h1 is the spectrum of image0 + i image1; summed
 // over the target and over the interferers: zo[b][0] = T0 + i T1, zo[b][1] = I0 + i I1.
 __global__ void __launch_bounds__(256) room_product_kernel(const double2* zf, double2* zo,
-                                                           int n_src, int Lc, long long sb) {
+                                                           int n_src, int Lc, long long sb,
+                                                           const int* __restrict__ live) {
   const int k = blockIdx.x * 256 + threadIdx.x;
   if (k >= Lc) return;
   const int b = blockIdx.y;
@@ -707,6 +757,7 @@ __global__ void __launch_bounds__(256) room_product_kernel(const double2* zf, do
   const double2* zb = zf + (long long)b * sb;
   double2 T = {0, 0}, I = {0, 0};
   for (int s = 0; s < n_src; ++s) {
+    if (!live[(long long)b * n_src + s]) continue;
     const double2* zp = zb + (long long)(s >> 1) * Lc;
     const double2 z = zp[k], zc = zp[kp];
     double2 Y;
@@ -756,14 +807,19 @@ extern "C" int avz_scene_fft_len(int n) {
   return n > 1 && fft_factor(n, rad) > 0;
 }
 
-// Workspace of the mixing back end: FFT path 2 x [B][max(ceil(n_src/2), 2)][n] double2;
-// fallback: fp32 kernels + images [B][n_src][2][n] each, and [B][2][n] double2.
+// The live flags [B][n_src] int behind the packed transforms.
+static long long live_bytes(int batch, int n_src) {
+  return ((long long)batch * n_src * (long long)sizeof(int) + 255) & ~255LL;
+}
+
+// Workspace of the mixing back end: FFT path 2 x [B][max(ceil(n_src/2), 2)][n] double2 and
+// the live flags; fallback: fp32 kernels + images [B][n_src][2][n] each, and [B][2][n] double2.
 extern "C" long long avz_scene_mix_ws(int batch, int n_src, int n) {
   int rad[32];
   const long long B = batch, N = n;
   if (fft_factor(n, rad) > 0) {
     const long long nz = std::max((n_src + 1) / 2, 2);
-    return 2 * B * nz * N * (long long)sizeof(double2);
+    return 2 * B * nz * N * (long long)sizeof(double2) + live_bytes(batch, n_src);
   }
   return 2 * B * n_src * 2 * N * (long long)sizeof(float) + B * 2 * N * (long long)sizeof(double2);
 }
@@ -778,11 +834,14 @@ extern "C" int avz_launch_scene(const SceneArgs* a, void* ws, void* stream) {
     double2* z0 = static_cast<double2*>(ws);
     double2* z1 = z0 + (long long)B * sb;
     const int P = (a->n_src + 1) / 2;
-    hipLaunchKernelGGL(scene_pack_kernel, dim3((n + 255) / 256, B, P), dim3(256), 0, st, *a, z0, sb);
+    int* live = reinterpret_cast<int*>(z1 + (long long)B * sb);
+    if (hipMemsetAsync(live, 0, (size_t)B * a->n_src * sizeof(int), st) != hipSuccess) return -3;
+    hipLaunchKernelGGL(scene_pack_kernel, dim3((n + 255) / 256, B, P), dim3(256), 0, st, *a, z0, sb,
+                       live);
     double2* f = fft_run(z0, z1, n, B, P, sb, -1.0, st);
     double2* o = (f == z0) ? z1 : z0;
     hipLaunchKernelGGL(scene_phase_kernel, dim3((n / 2 + 1 + 255) / 256, B), dim3(256), 0, st, *a,
-                       (const double2*)f, o, sb);
+                       (const double2*)f, o, sb, (const int*)live);
     double2* t = fft_run(o, f, n, B, 2, sb, 1.0, st);
     hipLaunchKernelGGL(avz_scene_mix_kernel, dim3(B), dim3(kMixThreads), 0, st, *a,
                        (const double2*)t, sb, n);
@@ -820,6 +879,9 @@ extern "C" long long avz_scene_gen_ws(int batch, int n_src, int n) {
 
 // Front end of both generators: the sources and the noise of utterances start .. start +
 // B - 1 (and the anechoic azimuths) into the scratch at ws; returns the first byte after it.
+// The back ends write only behind the returned pointer, so after a generate call the head of
+// the workspace still holds sources [B][S][n] fp32, noise [B][2][n] fp32 and angles [B][S]
+// fp64, each padded to 256 B: tests/test_gpu_scene_stages.py reads them back there.
 static char* gen_front(SceneArgs* a, long long start, uint32_t seed, void* ws, hipStream_t st,
                        GenArgs& g) {
   const int B = a->batch, S = a->n_src, n = a->n;
@@ -900,10 +962,11 @@ extern "C" int avz_launch_room_rir(const RoomArgs* r, int batch, int n_src, cons
 }
 
 // Workspace of the reverberant back end: 2 x [B][ceil(n_src/2) + n_src][Lc] double2 (the
-// packed sources and the packed RIRs, ping-pong).
+// packed sources and the packed RIRs, ping-pong) and the live flags.
 extern "C" long long avz_scene_reverb_ws(const RoomArgs* r, int batch, int n_src, int n) {
   const long long nz = (n_src + 1) / 2 + n_src;
-  return 2LL * batch * nz * avz_room_conv_len(n, r->rir_len) * (long long)sizeof(double2);
+  return 2LL * batch * nz * avz_room_conv_len(n, r->rir_len) * (long long)sizeof(double2) +
+         live_bytes(batch, n_src);
 }
 
 extern "C" int avz_launch_scene_reverb(const RoomArgs* r, const SceneArgs* a, void* ws,
@@ -914,7 +977,10 @@ extern "C" int avz_launch_scene_reverb(const RoomArgs* r, const SceneArgs* a, vo
   const long long sb = (long long)(P + S) * Lc;
   double2* z0 = static_cast<double2*>(ws);
   double2* z1 = z0 + (long long)B * sb;
-  hipLaunchKernelGGL(room_pack_kernel, dim3((Lc + 255) / 256, B, P), dim3(256), 0, st, *a, z0, sb, Lc);
+  int* live = reinterpret_cast<int*>(z1 + (long long)B * sb);
+  if (hipMemsetAsync(live, 0, (size_t)B * S * sizeof(int), st) != hipSuccess) return -3;
+  hipLaunchKernelGGL(room_pack_kernel, dim3((Lc + 255) / 256, B, P), dim3(256), 0, st, *a, z0, sb, Lc,
+                     live);
   // RIRs straight into the packed layout: mic 0 the real part, mic 1 the imaginary part
   room_rir_launch(r, B, S, a->angles_deg,
                   RirOut{reinterpret_cast<double*>(z0 + (long long)P * Lc), 2 * sb, 2LL * Lc, 1, 2}, st);
@@ -924,7 +990,7 @@ extern "C" int avz_launch_scene_reverb(const RoomArgs* r, const SceneArgs* a, vo
   double2* f = fft_run(z0, z1, Lc, B, P + S, sb, -1.0, st);
   double2* o = (f == z0) ? z1 : z0;
   hipLaunchKernelGGL(room_product_kernel, dim3((Lc + 255) / 256, B), dim3(256), 0, st,
-                     (const double2*)f, o, S, Lc, sb);
+                     (const double2*)f, o, S, Lc, sb, (const int*)live);
   double2* t = fft_run(o, f, Lc, B, 2, sb, 1.0, st);
   hipLaunchKernelGGL(avz_scene_mix_kernel, dim3(B), dim3(kMixThreads), 0, st, *a,
                      (const double2*)t, sb, Lc);
