@@ -666,6 +666,64 @@ typedef struct avz_wpe_stream_args {
 } avz_wpe_stream_args;
 int avz_wpe_stream_push(const avz_plan* plan, const avz_wpe_stream_args* args, void* hip_stream);
 
+/* ------------------------------------------------------------------ blind delay-histogram mask
+ * A target-probability mask for AVZ_MASK_EXTERNAL plans that needs neither references nor a
+ * trained model: the delay-only form of DUET (Yilmaz & Rickard 2004). The algorithm is the
+ * contract (avz/delay_mask.py delay_mask_numpy is the fp64 restatement).
+ * The plan supplies N = n_fft, H = N / 2, F = H + 1, fs, d = mic_d and c = c_sound; its mask
+ * mode, beamformer and post-filter are ignored. Y0, Y1: the two mic spectra of avz_stft.
+ * omega_k = 2 pi k / N; delta_max = d fs / c samples; R = 1.25 delta_max; hist_bins bins of
+ * width D = 2 R / hist_bins, bin i centred at -R + (i + 1/2) D. With mic 0 at +d/2 a far-field
+ * source at azimuth theta gives Y1 / Y0 = e^{+i omega_k delta}, delta = delta_max cos(theta).
+ *  1. Histogram, per utterance: for k_lo = max(1, ceil(f_lo_hz N / fs)) <= k <= k_hi =
+ *     min(N / 2, ceil(N / (2 R)) - 1) (no delay inside the range aliases) and every frame:
+ *     X = Y1 conj(Y0), w = |X|, delta = arg(X) / omega_k, u = (delta + R) / D - 1/2,
+ *     i0 = floor(u), phi = u - i0; h[i0] += (1 - phi) w and h[i0 + 1] += phi w, each where the
+ *     index lies in 0 .. hist_bins - 1. A pair whose u or w is not finite deposits nothing.
+ *     k_hi < k_lo: h = 0. The spectra and w are fp32 (atan2f); h is summed in fp64.
+ *  2. Peaks (fp64): `smooth` passes of hs[i] = hs[i-1]/4 + hs[i]/2 + hs[i+1]/4 (zeros
+ *     outside). Bin i is a candidate when max hs > 0, hs[i] > hs[i-1], hs[i] >= hs[i+1] and
+ *     hs[i] >= rel_height max hs; its delay is -R + (i + 1/2 + o) D with l = hs[i-1],
+ *     r = hs[i+1], o = (l - r) / (2 (l - 2 hs[i] + r)), or 0 when that denominator is 0.
+ *     Candidates with |delay - delta_t| <= min_sep delta_max, delta_t = delta_max
+ *     cos(angle), are the target itself and are dropped; of the others the J <= max_peaks
+ *     highest are kept (ties: the lower bin first). The list is delta_0 = delta_t (always the
+ *     geometric value) followed by the J kept delays, highest first.
+ *  3. Mask, for every bin 0 .. F - 1 and every frame: cost_j = |Y1 - e^{i omega_k delta_j}
+ *     Y0|^2 (fp32; rotations from fp64); M = 0 if some j >= 1 has cost_j < cost_0 strictly,
+ *     else 1. Ties, k = 0, an all-zero mixture, J = 0 and NaNs all give 1.
+ * M is the target probability ext_mask takes (noise weight 1 - M). Frames past an utterance's
+ * own count are not written (as avz_stft); a row with len < n_fft is not processed: its
+ * n_peaks is -1 and nothing else of it is written.
+ * Checks, all on the host before any HIP call (avz_delay_mask_check runs them on a bare
+ * configuration): a NULL plan, args, len, mix, mask or workspace, hist_bins even or outside
+ * 9 .. 257, smooth outside 0 .. 8, max_peaks outside 0 .. 7, rel_height outside (0, 1],
+ * min_sep or f_lo_hz negative or NaN: AVZ_ERR_ARG; batch outside 1 .. max_batch, max_len
+ * outside [n_fft, max_samples], ch_stride < max_len, (batch > 1) mix_stride < ch_stride +
+ * max_len, mask strides that are not positive or let two of the F x T elements of a row (or
+ * two rows) share an address, or workspace_bytes too small: AVZ_ERR_SHAPE; workspace not
+ * 256-byte aligned: AVZ_ERR_ALIGN. No call allocates device memory.
+ * Guarantees: results are bit-identical from call to call, whatever the utterance's index and
+ * whatever the other utterances hold (a NaN in one never reaches another); scaling a mixture
+ * by a power of two changes neither its delays nor its mask. */
+typedef struct avz_delay_mask_args {
+  int batch; const int* len; int max_len;           /* as avz_stft */
+  const float* mix; long long mix_stride, ch_stride;
+  const double* angle_deg;     /* optional device [batch]: target azimuth per utterance (the
+                                  camera's); NULL = the plan's angle_deg */
+  int hist_bins, smooth, max_peaks;  /* odd 9..257; 0..8; 0..7 */
+  double rel_height, min_sep, f_lo_hz;  /* (0, 1]; >= 0; >= 0 */
+  float* mask; long long mask_stride_b, mask_stride_f, mask_stride_t;  /* ext_mask's layout */
+  double* hist_out;            /* optional [batch][hist_bins]: h before smoothing */
+  double* delays_out;          /* optional [batch][8]: delta_t, then the J kept delays, NaN-padded */
+  int* n_peaks;                /* optional [batch]: J, or -1 for a row with len < n_fft */
+  void* workspace; long long workspace_bytes;       /* 256-byte aligned */
+} avz_delay_mask_args;
+long long avz_delay_mask_workspace_bytes(const avz_plan* plan, int batch, int max_len,
+                                         int hist_bins);
+int avz_delay_mask(const avz_plan* plan, const avz_delay_mask_args* args, void* hip_stream);
+int avz_delay_mask_check(const avz_config* cfg, const avz_delay_mask_args* args); /* host checks only */
+
 const char* avz_strerror(int code);
 /* Last HIP error string recorded by the library on this thread (diagnostics). */
 const char* avz_last_hip_error(void);

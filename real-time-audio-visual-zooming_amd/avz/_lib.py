@@ -49,6 +49,7 @@ EXPORTED = [
     "avz_mask_training_batch",
     "avz_stream_state_bytes", "avz_stream_reset", "avz_stream_steer", "avz_stream_push",
     "avz_wpe_stream_state_bytes", "avz_wpe_stream_reset", "avz_wpe_stream_push",
+    "avz_delay_mask_workspace_bytes", "avz_delay_mask", "avz_delay_mask_check",
 ]
 
 
@@ -140,6 +141,20 @@ class AvzWpeStreamArgs(ct.Structure):
         ("out", ct.c_void_p), ("out_stride", ct.c_longlong), ("out_ch_stride", ct.c_longlong),
         ("Y_out", ct.c_void_p), ("Z_out", ct.c_void_p), ("G_out", ct.c_void_p),
         ("state", ct.c_void_p), ("state_bytes", ct.c_longlong),
+    ]
+
+
+class AvzDelayMaskArgs(ct.Structure):
+    _fields_ = [
+        ("batch", ct.c_int), ("len", ct.c_void_p), ("max_len", ct.c_int),
+        ("mix", ct.c_void_p), ("mix_stride", ct.c_longlong), ("ch_stride", ct.c_longlong),
+        ("angle_deg", ct.c_void_p),
+        ("hist_bins", ct.c_int), ("smooth", ct.c_int), ("max_peaks", ct.c_int),
+        ("rel_height", ct.c_double), ("min_sep", ct.c_double), ("f_lo_hz", ct.c_double),
+        ("mask", ct.c_void_p), ("mask_stride_b", ct.c_longlong),
+        ("mask_stride_f", ct.c_longlong), ("mask_stride_t", ct.c_longlong),
+        ("hist_out", ct.c_void_p), ("delays_out", ct.c_void_p), ("n_peaks", ct.c_void_p),
+        ("workspace", ct.c_void_p), ("workspace_bytes", ct.c_longlong),
     ]
 
 
@@ -267,6 +282,12 @@ def _load():
     for name in ("avz_wpe_stream_reset", "avz_wpe_stream_push", "avz_wpe_stream_check_reset",
                  "avz_wpe_stream_check_push"):
         getattr(lib, name).restype = ct.c_int
+    DA = ct.POINTER(AvzDelayMaskArgs)
+    lib.avz_delay_mask_workspace_bytes.argtypes = [P, I, I, I]
+    lib.avz_delay_mask_workspace_bytes.restype = LL
+    lib.avz_delay_mask.argtypes = [P, DA, P]
+    lib.avz_delay_mask_check.argtypes = [CP, DA]
+    lib.avz_delay_mask.restype = lib.avz_delay_mask_check.restype = ct.c_int
     lib.avz_stoi_taps.argtypes = [DP]
     lib.avz_stoi_taps.restype = ct.c_int
     lib.avz_strerror.argtypes = [ct.c_int]

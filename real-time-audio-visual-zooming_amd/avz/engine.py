@@ -600,6 +600,76 @@ def wpe_stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out:
     return out
 
 
+def delay_mask_workspace_bytes(plan: MVDRPlan, batch: int, max_len: int,
+                               hist_bins: int = 65) -> int:
+    return check(lib.avz_delay_mask_workspace_bytes(plan._h, int(batch), int(max_len),
+                                                    int(hist_bins)),
+                 "avz_delay_mask_workspace_bytes")
+
+
+def delay_mask(plan: MVDRPlan, mix: torch.Tensor, lengths=None, angles=None, *, hist_bins=65,
+               smooth=3, rel_height=0.25, min_sep=0.2, max_peaks=3, f_lo=100.0, max_len=None,
+               mask=None, workspace=None, return_debug=False, stream=None):
+    """Blind delay-histogram (DUET-style) target mask of a [B, 2, S] mic pair
+    (avz_delay_mask; include/avz.h): float32 [B, F, T], the target
+    probability an external-mask plan takes as ``ext_mask``. Only the plan's n_fft, fs, mic_d,
+    c_sound and angle_deg matter. ``angles``: optional float64 [B] device tensor, the target
+    azimuth per utterance. ``mask``: optional output (any strides; frames past an utterance's
+    own count and rows shorter than n_fft are left as they are; a new one starts as zeros).
+    ``workspace``: optional uint8 device tensor of delay_mask_workspace_bytes(...) bytes (one
+    is allocated otherwise). With ``return_debug`` also returns hist [B, hist_bins] float64
+    (before smoothing), delays [B, 8] float64 (delta_t, the kept delays, NaN) and n_peaks [B]
+    int32 (-1: row shorter than n_fft)."""
+    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or mix.stride(2) != 1 \
+            or not mix.is_cuda:
+        raise ValueError("mix must be float32 [B, 2, S] on the device")
+    B, _, S = mix.shape
+    dev = mix.device
+    if lengths is None:
+        lengths = torch.full((B,), S, dtype=torch.int32, device=dev)
+        max_len = S
+    if lengths.dtype != torch.int32 or lengths.device != dev or not lengths.is_contiguous():
+        raise ValueError("lengths must be a contiguous int32 [B] tensor on the mixture's device")
+    if max_len is None:
+        max_len = int(lengths.max().item())
+    if angles is not None and (angles.dtype != torch.float64 or angles.numel() < B
+                               or not angles.is_contiguous() or angles.device != dev):
+        raise ValueError("angles must be a contiguous float64 [B] tensor on the mixture's device")
+    T = n_frames(int(max_len), plan.hop)
+    if mask is None:
+        mask = torch.zeros((B, plan.F, T), dtype=torch.float32, device=dev)
+    if mask.dtype != torch.float32 or mask.dim() != 3 or mask.shape[0] != B \
+            or mask.shape[1] < plan.F or mask.shape[2] < T or mask.device != dev:
+        raise ValueError(f"mask must be float32 [{B}, >= {plan.F}, >= {T}] on the mixture's device")
+    ws = workspace
+    if ws is None:
+        ws = torch.empty(delay_mask_workspace_bytes(plan, B, max_len, hist_bins),
+                         dtype=torch.uint8, device=dev)
+    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
+        raise ValueError("workspace must be a contiguous uint8 tensor on the mixture's device")
+    a = _lib.AvzDelayMaskArgs()
+    a.batch, a.len, a.max_len = B, lengths.data_ptr(), int(max_len)
+    a.mix, a.mix_stride, a.ch_stride = mix.data_ptr(), mix.stride(0), mix.stride(1)
+    a.angle_deg = None if angles is None else angles.data_ptr()
+    a.hist_bins, a.smooth, a.max_peaks = int(hist_bins), int(smooth), int(max_peaks)
+    a.rel_height, a.min_sep, a.f_lo_hz = float(rel_height), float(min_sep), float(f_lo)
+    a.mask = mask.data_ptr()
+    a.mask_stride_b, a.mask_stride_f, a.mask_stride_t = mask.stride()
+    hist = delays = n_peaks = None
+    if return_debug:
+        hist = torch.zeros((B, int(hist_bins)), dtype=torch.float64, device=dev)
+        delays = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev)
+        n_peaks = torch.zeros(B, dtype=torch.int32, device=dev)
+        a.hist_out, a.delays_out, a.n_peaks = hist.data_ptr(), delays.data_ptr(), n_peaks.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    with torch.cuda.device(dev):
+        check(lib.avz_delay_mask(plan._h, ct.byref(a), _stream_handle(stream)), "avz_delay_mask")
+    if workspace is None:
+        ws.record_stream(stream if stream is not None else torch.cuda.current_stream(dev))
+    out = mask[:, :plan.F, :T]
+    return (out, hist, delays, n_peaks) if return_debug else out
+
+
 def srp_scan(plan: MVDRPlan, mix: torch.Tensor, lengths=None, max_len=None, n_angles=181,
              angle_lo=0.0, angle_hi=180.0, f_lo=200.0, f_hi=4000.0, stream=None):
     """scripts/debug_srp.py:46-62 for a [B, 2, S] batch -> power map [B, n_angles] in dB

@@ -15,6 +15,7 @@
 
 #include "../../include/avz.h"
 #include "avz_internal.h"
+#include "avz_delay_mask.hpp"
 
 // Per-call device workspace of the chain (see avz_internal.h ChainArgs), carved from one
 // caller-provided block (avz_mvdr_workspace_bytes) or from the plan's own arena.
@@ -1560,6 +1561,108 @@ extern "C" int avz_wpe_stream_push(const avz_plan* p, const avz_wpe_stream_args*
   s.state = static_cast<unsigned char*>(a->state);
   s.state_stride = avz::WpeStreamLayout(c.n_fft, a->taps, a->delay).stride;
   rc = avz_launch_wpe_stream_push(c.n_fft, &s, p->xwin, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+// ------------------------------------------------------------------ blind delay-histogram mask
+// As the streaming entry points: every check runs on the host before any HIP call, and
+// avz_delay_mask_check takes the configuration itself (tests without a device).
+static int delay_param_check(int hist_bins) {
+  if (hist_bins < 9 || hist_bins > avz::kDelayMaxBins || !(hist_bins & 1)) return AVZ_ERR_ARG;
+  return AVZ_OK;
+}
+
+static long long delay_workspace_bytes(const avz_config& c, int batch, int max_len,
+                                       int hist_bins) {
+  const int rc = delay_param_check(hist_bins);
+  if (rc != AVZ_OK) return rc;
+  if (batch < 1 || batch > c.max_batch) return AVZ_ERR_SHAPE;
+  if (max_len < c.n_fft || max_len > c.max_samples) return AVZ_ERR_SHAPE;
+  return avz::DelayLayout(batch, frames_for(max_len, c.hop), hist_bins).bytes;
+}
+
+extern "C" long long avz_delay_mask_workspace_bytes(const avz_plan* p, int batch, int max_len,
+                                                    int hist_bins) {
+  if (!p) return AVZ_ERR_ARG;
+  return delay_workspace_bytes(p->cfg, batch, max_len, hist_bins);
+}
+
+extern "C" int avz_delay_mask_check(const avz_config* cfg, const avz_delay_mask_args* a) {
+  if (!cfg || !a) return AVZ_ERR_ARG;
+  const avz_config& c = *cfg;
+  if (!a->len || !a->mix || !a->mask || !a->workspace) return AVZ_ERR_ARG;
+  int rc = delay_param_check(a->hist_bins);
+  if (rc != AVZ_OK) return rc;
+  if (a->smooth < 0 || a->smooth > 8 || a->max_peaks < 0 || a->max_peaks > avz::kDelayList - 1)
+    return AVZ_ERR_ARG;
+  if (!(a->rel_height > 0.0 && a->rel_height <= 1.0)) return AVZ_ERR_ARG;  // NaN included
+  if (!(a->min_sep >= 0.0) || !(a->f_lo_hz >= 0.0)) return AVZ_ERR_ARG;
+  if (a->batch < 1 || a->batch > c.max_batch) return AVZ_ERR_SHAPE;
+  if (a->max_len < c.n_fft || a->max_len > c.max_samples) return AVZ_ERR_SHAPE;
+  if (a->ch_stride < a->max_len) return AVZ_ERR_SHAPE;
+  if (a->batch > 1 && a->mix_stride < a->ch_stride + a->max_len) return AVZ_ERR_SHAPE;
+  const long long T = frames_for(a->max_len, c.hop), F = c.n_fft / 2 + 1;
+  const long long sf = a->mask_stride_f, st = a->mask_stride_t;
+  if (sf < 1 || st < 1) return AVZ_ERR_SHAPE;
+  const bool t_fastest = sf >= T * st, f_fastest = st >= F * sf;
+  if (!t_fastest && !f_fastest) return AVZ_ERR_SHAPE;
+  if (a->batch > 1 && a->mask_stride_b < (t_fastest ? F * sf : T * st)) return AVZ_ERR_SHAPE;
+  if (a->workspace_bytes < delay_workspace_bytes(c, a->batch, a->max_len, a->hist_bins))
+    return AVZ_ERR_SHAPE;
+  if (misaligned(a->workspace, 256)) return AVZ_ERR_ALIGN;
+  if (misaligned(a->mix, 4) || misaligned(a->mask, 4) || misaligned(a->len, 4) ||
+      misaligned(a->angle_deg, 8) || misaligned(a->hist_out, 8) ||
+      misaligned(a->delays_out, 8) || misaligned(a->n_peaks, 4))
+    return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+extern "C" int avz_delay_mask(const avz_plan* p, const avz_delay_mask_args* a, void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = avz_delay_mask_check(&p->cfg, a);
+  if (rc != AVZ_OK) return rc;
+  const avz_config& c = p->cfg;
+  const int N = c.n_fft;
+  avz::DelayArgs k{};
+  k.batch = a->batch;
+  k.len = a->len;
+  k.max_len = a->max_len;
+  k.max_frames = frames_for(a->max_len, c.hop);
+  const avz::DelayLayout lay(a->batch, k.max_frames, a->hist_bins);
+  k.nblk = lay.nblk;
+  k.mix = a->mix;
+  k.mix_stride = a->mix_stride;
+  k.ch_stride = a->ch_stride;
+  k.angle_deg = a->angle_deg;
+  k.plan_angle = c.angle_deg;
+  k.nb = a->hist_bins;
+  k.smooth = a->smooth;
+  k.max_peaks = a->max_peaks;
+  k.rel_height = a->rel_height;
+  k.min_sep = a->min_sep;
+  k.dmax = c.mic_d * (double)c.fs / c.c_sound;
+  k.R = 1.25 * k.dmax;
+  k.bin_w = 2.0 * k.R / a->hist_bins;
+  const double lo = std::ceil(a->f_lo_hz * N / (double)c.fs);
+  k.k_lo = lo >= N ? N : std::max(1, (int)lo);  // above N / 2: an empty band
+  k.k_hi = -1;  // empty band: no spacing, no delay to find
+  if (k.R > 0.0 && std::isfinite(k.R)) {
+    const double lim = std::ceil(N / (2.0 * k.R)) - 1.0;  // largest k with omega_k R < pi
+    k.k_hi = lim >= N / 2 ? N / 2 : (int)lim;
+  }
+  k.mask = a->mask;
+  k.m_sb = a->mask_stride_b;
+  k.m_sf = a->mask_stride_f;
+  k.m_st = a->mask_stride_t;
+  k.hist_out = a->hist_out;
+  k.delays_out = a->delays_out;
+  k.n_peaks = a->n_peaks;
+  char* ws = static_cast<char*>(a->workspace);
+  k.part = reinterpret_cast<double*>(ws + lay.part_off);
+  k.list = reinterpret_cast<double*>(ws + lay.list_off);
+  k.count = reinterpret_cast<int*>(ws + lay.count_off);
+  rc = avz_launch_delay_mask(N, &k, stream);
   if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
   return rc;
 }
