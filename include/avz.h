@@ -120,10 +120,15 @@ typedef struct avz_plan avz_plan;
  * (IPD) and full_audio_generating_pipeline/inference.py:88-118 (external mask):
  * STFT -> mask -> masked covariance -> MVDR solve -> apply + post-filter -> iSTFT
  * (-> peak normalise). out[b] has (ceil(len[b]/hop)) * hop samples
- * (scipy.signal.istft length). */
+ * (scipy.signal.istft length); nothing of the row is written past them.
+ * A row shorter than a frame (len[b] < n_fft, 0 included; scipy needs nperseg <= len) is
+ * skipped, on every kernel path of the chain: its row of out is not written at all and
+ * peak[b] is NaN (as the rows avz_srp_scan and avz_delay_mask do not process). Its
+ * neighbours in the batch are computed as if it were not there. */
 typedef struct avz_batch_args {
   int batch;
-  const int* len;          /* [batch] samples per utterance (device), n_fft <= len <= max_samples */
+  const int* len;          /* [batch] samples per utterance (device), n_fft <= len <= max_samples;
+                              a shorter row is skipped (above)                                  */
   int max_len;             /* host-side upper bound of len[] (validated against strides)         */
   const float* mix;        /* [batch][2][ch_stride]: mic channels planar (y_mix [2,S])          */
   long long mix_stride;    /* elements between utterances                                       */
@@ -135,7 +140,8 @@ typedef struct avz_batch_args {
   long long mask_stride_b, mask_stride_f, mask_stride_t;
   float* out;              /* [batch][out_stride], out_stride % 4 == 0, 16-byte aligned          */
   long long out_stride;
-  float* peak;             /* [batch] max|out| before normalisation, or NULL                    */
+  float* peak;             /* [batch] max|out| before normalisation (NaN for a skipped row), or
+                              NULL                                                               */
   double* cov_out;         /* debug: [batch][F][5] sum m|y0|^2, sum m|y1|^2, Re/Im sum m y0 y1*,
                               sum m   (or NULL)                                                  */
   float* w_out;            /* debug: [batch][F][4] Re w0, Im w0, Re w1, Im w1 (or NULL)         */

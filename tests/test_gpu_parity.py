@@ -337,8 +337,11 @@ def test_ipd_identical_channels(avz, gpu_device):
 def test_multi_round_ragged_batch_equals_single_runs(avz, gpu_device, mask, n_fft):
     """A batch larger than one pass of the persistent grids (300 utterances against 256
     per-utterance synthesis blocks and 2-3 analysis blocks per CU, so blocks loop over
-    several utterances / items of different lengths) with ragged lengths, for both
-    per-utterance synthesis kernels (N = 1024, 512) and the IPD plan (no post-filter).
+    several utterances / items of different lengths) with ragged lengths, for the N = 1024
+    per-utterance synthesis kernel (IBM, and the IPD plan without a post-filter) and, at
+    N = 512, the chunk grid + finalize: 300 is no multiple of the CU count, and the N = 512
+    per-utterance kernel takes whole rounds only (test_gpu_utt_rounds.py runs it on ragged
+    batches). The first run asserts which kernels it launched (utt_cases.assert_path).
     The partial last rounds are split into pieces (analysis items into step ranges whose
     covariance partials the solve sums in fp64; at N = 1024 the last 44 utterances'
     synthesis into step pieces with a seam finalize), and a single run splits its one
@@ -358,7 +361,11 @@ def test_multi_round_ragged_batch_equals_single_runs(avz, gpu_device, mask, n_ff
     plan = avz.MVDRPlan(max_batch=B, **kw)
     lt = torch.from_numpy(lens).to(gpu_device)
     refs = dict(ref_tgt=dt, ref_int=di) if mask == "ibm" else {}
-    out, peak = plan.run(dm, lt, max_len=S, **refs)
+    # N = 1024: the per-utterance kernel solves in-block (no solve launch; its pieces bring a
+    # finalize launch only below the CU count); N = 512: all four kernels
+    import utt_cases
+    path = dict(solve=False, finalize=None) if n_fft == 1024 else dict(solve=True, finalize=True)
+    out, peak = utt_cases.assert_path(plan, lambda: plan.run(dm, lt, max_len=S, **refs), **path)
     out, peak = out.clone(), peak.clone()
     out2, peak2 = plan.run(dm, lt, max_len=S, **refs)  # run to run: bitwise
     torch.testing.assert_close(out2, out, rtol=0, atol=0, equal_nan=True)
