@@ -730,6 +730,82 @@ long long avz_delay_mask_workspace_bytes(const avz_plan* plan, int batch, int ma
 int avz_delay_mask(const avz_plan* plan, const avz_delay_mask_args* args, void* hip_stream);
 int avz_delay_mask_check(const avz_config* cfg, const avz_delay_mask_args* args); /* host checks only */
 
+/* ------------------------------------------------------------------ streaming blind delay mask
+ * avz_delay_mask hop by hop: a recursive histogram with causal labels, on the frames
+ * avz_stream_push forms, so that its mask feeds an AVZ_MASK_EXTERNAL plan's avz_stream_push of
+ * the same hops. The algorithm is the contract (avz/delay_mask.py
+ * delay_mask_stream_numpy is the fp64 restatement). From the plan: N = n_fft, H = N / 2,
+ * F = H + 1, fs, d = mic_d, c = c_sound, max_batch; its mask mode, beamformer, post-filter and
+ * normalisation are ignored. The grid is avz_delay_mask's, unchanged: omega_k, delta_max,
+ * R = 1.25 delta_max, hist_bins bins of width D, the band k_lo .. k_hi.
+ * Per stream, x_t is the t-th hop pushed since the last reset (two mics) and x_-1 = 0. For
+ * every frame t, in order:
+ *  1. Frame. Y_t is the frame avz_stream_push forms: [x_t-1 | x_t] under the plan's fp32
+ *     periodic Hann, scaled by 1 / sum(w).
+ *  2. Deposit. d_t[i] is avz_delay_mask's stage 1 restricted to frame t's band bins: u, w and
+ *     the two-bin split in fp32 (w = |Y0| |Y1|, atan2f); the deposits of one frame are summed
+ *     in fp64 in an order that depends on the frame alone. A pair whose u or w is not finite
+ *     deposits nothing.
+ *  3. Recursion (fp64, state): h_t = forget h_t-1 + d_t where the stream's adapt flag is
+ *     non-zero, else h_t = h_t-1 (the histogram freezes, for example while the target is known
+ *     absent); h_-1 = 0.
+ *  4. Peaks. avz_delay_mask's stage 2 on h_t with the call's smooth, rel_height, min_sep and
+ *     max_peaks and the stream's target azimuth: the list (delta_0 = delta_max cos(theta), then
+ *     the J_t kept delays).
+ *  5. Labels. avz_delay_mask's stage 3 on frame t with the list of step 4: every bin
+ *     0 .. F - 1, the rotations from fp64. Ties, k = 0, a zero frame, J_t = 0 and NaNs give 1.
+ *     M[:, t] uses frames <= t only: it is causal.
+ * Relation to the offline mask: with forget = 1, after a signal of T hops plus one drain hop
+ * of zeros, h is the offline histogram of that T H-sample signal (the frames are scipy's padded
+ * frames; up to fp64 association and the two transforms' fp32 rounding). With forget < 1, h
+ * tracks moving interferers. Scaling a stream's input by a power of two changes no delay and
+ * no label.
+ * The state is one caller-owned device buffer of avz_delay_stream_state_bytes(plan, streams,
+ * hist_bins) bytes, 256-byte aligned; its layout is private. Per stream: a 64-byte header (the
+ * 64-bit frame count, hist_bins, n_fft), the previous hop of both mics [2][H] f32 and h
+ * [hist_bins] f64, rounded up to 256 bytes: 4864 bytes per stream at N = 1024, hist_bins = 65
+ * (2816 at N = 512).
+ *  avz_delay_stream_reset  starts the selected streams (select[s] != 0; NULL = all): zero
+ *                          history, h = 0. hist_bins is fixed here: it is recorded in each
+ *                          stream's header and, on the host, against the buffer's address. A
+ *                          partial reset (select != NULL) must repeat the buffer's hist_bins.
+ *  avz_delay_stream_push   `hops` >= 1 new hops per stream; mask gets one column per hop. A
+ *                          push whose hist_bins differs from that record, or a push on a
+ *                          buffer never reset in this process, returns AVZ_ERR_ARG; the kernel
+ *                          also leaves a stream untouched when its header differs. A stream
+ *                          with active[s] == 0 keeps its state, and its rows of every output
+ *                          stay unwritten.
+ * Checks, all on the host before any HIP call (avz_delay_stream_check runs the push's on a bare
+ * configuration): a NULL plan, args, mix, mask or state, hops < 1, forget outside (0, 1],
+ * hist_bins even or outside 9 .. 257, smooth outside 0 .. 8, max_peaks outside 0 .. 7,
+ * rel_height outside (0, 1], min_sep or f_lo_hz negative or NaN: AVZ_ERR_ARG; streams outside
+ * 1 .. max_batch, ch_stride < hops * hop, (streams > 1) mix_stride < ch_stride + hops * hop,
+ * mask strides that are not positive or let two of the [streams][F][hops] elements share an
+ * address, or state_bytes too small: AVZ_ERR_SHAPE; state not 256-byte aligned: AVZ_ERR_ALIGN.
+ * Guarantees: a stream's masks, per-frame delay lists and whole final state are bit-identical
+ * however its hops are grouped into calls, whatever its index and whatever the other streams
+ * hold, as long as the per-call parameters stay the same; a NaN in one stream never reaches
+ * another; no call allocates device memory; no atomics and no inter-block traffic. */
+long long avz_delay_stream_state_bytes(const avz_plan* plan, int streams, int hist_bins);
+int avz_delay_stream_reset(const avz_plan* plan, void* state, long long state_bytes, int streams,
+                           int hist_bins, const int* select /* device or NULL = all */,
+                           void* hip_stream);
+typedef struct avz_delay_stream_args {
+  int streams, hops;                 /* hops >= 1 new hops per stream */
+  double forget;                     /* (0, 1] */
+  const int* active; const int* adapt;          /* device [streams] or NULL, as avz_stream_args */
+  const float* mix; long long mix_stride, ch_stride;   /* [streams][2][hops*hop] */
+  const double* angle_deg;           /* optional device [streams]; NULL or a NaN entry = the plan's */
+  int hist_bins, smooth, max_peaks; double rel_height, min_sep, f_lo_hz;   /* ranges of avz_delay_mask */
+  float* mask; long long mask_stride_b, mask_stride_f, mask_stride_t;     /* [streams][F][hops]: avz_stream_args.ext_mask's layout */
+  double* hist_out;                  /* optional [streams][hist_bins]: h after the call's last frame */
+  double* delays_out;                /* optional [streams][hops][8]: each frame's list, NaN-padded */
+  int* n_peaks;                      /* optional [streams][hops]: J_t */
+  void* state; long long state_bytes;
+} avz_delay_stream_args;
+int avz_delay_stream_push(const avz_plan* plan, const avz_delay_stream_args* args, void* hip_stream);
+int avz_delay_stream_check(const avz_config* cfg, const avz_delay_stream_args* args); /* host checks only */
+
 const char* avz_strerror(int code);
 /* Last HIP error string recorded by the library on this thread (diagnostics). */
 const char* avz_last_hip_error(void);

@@ -50,6 +50,8 @@ EXPORTED = [
     "avz_stream_state_bytes", "avz_stream_reset", "avz_stream_steer", "avz_stream_push",
     "avz_wpe_stream_state_bytes", "avz_wpe_stream_reset", "avz_wpe_stream_push",
     "avz_delay_mask_workspace_bytes", "avz_delay_mask", "avz_delay_mask_check",
+    "avz_delay_stream_state_bytes", "avz_delay_stream_reset", "avz_delay_stream_push",
+    "avz_delay_stream_check",
 ]
 
 
@@ -155,6 +157,21 @@ class AvzDelayMaskArgs(ct.Structure):
         ("mask_stride_f", ct.c_longlong), ("mask_stride_t", ct.c_longlong),
         ("hist_out", ct.c_void_p), ("delays_out", ct.c_void_p), ("n_peaks", ct.c_void_p),
         ("workspace", ct.c_void_p), ("workspace_bytes", ct.c_longlong),
+    ]
+
+
+class AvzDelayStreamArgs(ct.Structure):
+    _fields_ = [
+        ("streams", ct.c_int), ("hops", ct.c_int), ("forget", ct.c_double),
+        ("active", ct.c_void_p), ("adapt", ct.c_void_p),
+        ("mix", ct.c_void_p), ("mix_stride", ct.c_longlong), ("ch_stride", ct.c_longlong),
+        ("angle_deg", ct.c_void_p),
+        ("hist_bins", ct.c_int), ("smooth", ct.c_int), ("max_peaks", ct.c_int),
+        ("rel_height", ct.c_double), ("min_sep", ct.c_double), ("f_lo_hz", ct.c_double),
+        ("mask", ct.c_void_p), ("mask_stride_b", ct.c_longlong),
+        ("mask_stride_f", ct.c_longlong), ("mask_stride_t", ct.c_longlong),
+        ("hist_out", ct.c_void_p), ("delays_out", ct.c_void_p), ("n_peaks", ct.c_void_p),
+        ("state", ct.c_void_p), ("state_bytes", ct.c_longlong),
     ]
 
 
@@ -288,6 +305,14 @@ def _load():
     lib.avz_delay_mask.argtypes = [P, DA, P]
     lib.avz_delay_mask_check.argtypes = [CP, DA]
     lib.avz_delay_mask.restype = lib.avz_delay_mask_check.restype = ct.c_int
+    DS = ct.POINTER(AvzDelayStreamArgs)
+    lib.avz_delay_stream_state_bytes.argtypes = [P, I, I]
+    lib.avz_delay_stream_state_bytes.restype = LL
+    lib.avz_delay_stream_reset.argtypes = [P, P, LL, I, I, P, P]
+    lib.avz_delay_stream_push.argtypes = [P, DS, P]
+    lib.avz_delay_stream_check.argtypes = [CP, DS]
+    for name in ("avz_delay_stream_reset", "avz_delay_stream_push", "avz_delay_stream_check"):
+        getattr(lib, name).restype = ct.c_int
     lib.avz_stoi_taps.argtypes = [DP]
     lib.avz_stoi_taps.restype = ct.c_int
     lib.avz_strerror.argtypes = [ct.c_int]

@@ -6,6 +6,10 @@ test can feed perturbed ones. ``enhance_blind`` is the blind counterpart of
 ``masked_mvdr.enhance``: the device mask, then an external-mask MVDR plan with the floor
 post-filter (full_audio_generating_pipeline/inference.py:88-118 without its mask model).
 
+``delay_mask_stream_numpy`` / ``NumpyDelayStream`` restate the streaming form
+``avz_delay_stream_push`` with the same stage functions, one frame at a
+time: h_t = forget h_t-1 + d_t where the adapt flag is set, the peaks of h_t, frame t's labels.
+
 Steering convention (masked_mvdr.py:22-35, mic 0 at +d/2): a far-field source at azimuth theta
 gives Y1 / Y0 = exp(+i omega_k delta) with delta = delta_max cos(theta), delta_max = d fs / c.
 """
@@ -130,6 +134,72 @@ def delay_mask_numpy(Y0: np.ndarray, Y1: np.ndarray, n_fft: int, fs=16000, mic_d
     h = delay_histogram(Y0, Y1, g)
     delays, J, _ = delay_peaks(h, g, angle, smooth, rel_height, min_sep, max_peaks)
     return delay_labels(Y0, Y1, delays, J, n_fft), h, delays, J
+
+
+class NumpyDelayStream:
+    """One stream of the streaming delay mask in fp64, stateful: push() any number of hops at a
+    time (mix [2, hops H]; the frames are avz_stream_push's: [x_t-1 | x_t] under the fp32
+    periodic Hann scaled by 1 / sum(w)) or push_spectra() frames given as spectra [F, hops].
+    Every frame is computed on its own, so the results do not depend on the grouping. Both
+    return (M [F, hops] float32, h [hops, nb], lists [hops, 8], J [hops])."""
+
+    def __init__(self, n_fft, fs=16000, mic_d=0.08, c_sound=343.0, angle=90.0, hist_bins=65,
+                 smooth=3, rel_height=0.25, min_sep=0.2, max_peaks=3, f_lo=100.0, forget=1.0):
+        if not 0.0 < forget <= 1.0:
+            raise ValueError("forget must lie in (0, 1]")
+        self.n_fft, self.H, self.forget, self.angle = n_fft, n_fft // 2, float(forget), angle
+        self.grid = delay_grid(n_fft, fs, mic_d, c_sound, hist_bins, f_lo)
+        self.peak_kw = dict(smooth=smooth, rel_height=rel_height, min_sep=min_sep,
+                            max_peaks=max_peaks)
+        w = 0.5 + 0.5 * np.cos(np.linspace(-np.pi, np.pi, n_fft + 1)[:-1])
+        self.win32 = w.astype(np.float32).astype(np.float64)
+        self.reset()
+
+    def reset(self):
+        self.count = 0
+        self.prev = np.zeros((2, self.H))
+        self.h = np.zeros(self.grid.nb)
+
+    def steer(self, angle):
+        """New target azimuth (degrees) from the next pushed frame."""
+        self.angle = angle
+
+    def push_spectra(self, Y0, Y1, adapt=True):
+        T = Y0.shape[1]
+        flags = np.broadcast_to(np.asarray(adapt, bool), (T,))
+        M = np.empty((Y0.shape[0], T), np.float32)
+        hs, lists, Js = np.empty((T, self.grid.nb)), np.empty((T, LIST)), np.empty(T, np.int64)
+        for t in range(T):
+            y0, y1 = Y0[:, t:t + 1], Y1[:, t:t + 1]
+            if flags[t]:
+                self.h = self.forget * self.h + delay_histogram(y0, y1, self.grid)
+            delays, J, _ = delay_peaks(self.h, self.grid, self.angle, **self.peak_kw)
+            M[:, t] = delay_labels(y0, y1, delays, J, self.n_fft)[:, 0]
+            hs[t], lists[t], Js[t] = self.h, delays, J
+            self.count += 1
+        return M, hs, lists, Js
+
+    def push(self, mix, adapt=True):
+        mix = np.asarray(mix, dtype=np.float64)
+        H = self.H
+        hops = mix.shape[-1] // H
+        assert mix.shape == (2, hops * H) and hops >= 1
+        x = np.concatenate([self.prev, mix], axis=1)
+        Y = np.stack([[np.fft.rfft(x[m, j * H:j * H + 2 * H] * self.win32) / self.win32.sum()
+                       for j in range(hops)] for m in range(2)]).transpose(0, 2, 1)
+        self.prev = mix[:, -H:].copy()
+        return self.push_spectra(Y[0].astype(np.complex64), Y[1].astype(np.complex64), adapt)
+
+
+def delay_mask_stream_numpy(Y0: np.ndarray, Y1: np.ndarray, n_fft: int, fs=16000, mic_d=0.08,
+                            c_sound=343.0, hist_bins=65, smooth=3, rel_height=0.25, min_sep=0.2,
+                            max_peaks=3, f_lo=100.0, forget=1.0, adapt=None, angle=90.0):
+    """The streaming mask on one stream's frames Y0, Y1 [F, T] (complex64), one frame at a
+    time: (M [F, T] float32, h per frame [T, hist_bins], lists [T, 8], J [T]). adapt: per-frame
+    flags [T] (default all set): 0 freezes the histogram while the labels continue."""
+    st = NumpyDelayStream(n_fft, fs, mic_d, c_sound, angle, hist_bins, smooth, rel_height,
+                          min_sep, max_peaks, f_lo, forget)
+    return st.push_spectra(Y0, Y1, True if adapt is None else np.asarray(adapt, bool))
 
 
 def enhance_blind(y_mix: np.ndarray, n_fft=1024, mic_d=0.08, sigma=1e-5, angle=90.0,

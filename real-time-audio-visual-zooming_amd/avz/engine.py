@@ -670,6 +670,69 @@ def delay_mask(plan: MVDRPlan, mix: torch.Tensor, lengths=None, angles=None, *, 
     return (out, hist, delays, n_peaks) if return_debug else out
 
 
+# ------------------------------------------------------------------ streaming blind delay mask
+# Thin wrappers over avz_delay_stream_* (include/avz.h); avz/stream.py StreamingDelayMask owns
+# the state buffer and is the interface to use.
+def delay_stream_state_bytes(plan: MVDRPlan, streams: int, hist_bins: int = 65) -> int:
+    return check(lib.avz_delay_stream_state_bytes(plan._h, int(streams), int(hist_bins)),
+                 "avz_delay_stream_state_bytes")
+
+
+def delay_stream_reset(plan: MVDRPlan, state: torch.Tensor, streams: int, hist_bins: int = 65,
+                       select=None, stream=None):
+    """Start the selected streams (select: int32 [streams] device tensor, None = all): zero
+    history, h = 0; fixes the buffer's hist_bins."""
+    check(lib.avz_delay_stream_reset(plan._h, _ptr(state), state.numel(), int(streams),
+                                     int(hist_bins), _ptr(select), _stream_handle(stream)),
+          "avz_delay_stream_reset")
+
+
+def delay_stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, mask=None, *,
+                      forget: float = 1.0, angles=None, active=None, adapt=None, hist_bins=65,
+                      smooth=3, rel_height=0.25, min_sep=0.2, max_peaks=3, f_lo=100.0,
+                      hist_out=None, delays_out=None, n_peaks=None, stream=None):
+    """One avz_delay_stream_push: mix [streams, 2, hops * hop] float32 -> mask [streams, F, hops]
+    float32 (any strides; a new one starts as ones), the target probability the streaming
+    beamformer's push of the same hops takes. angles float64 [streams] (NaN = the plan's);
+    active / adapt int32 [streams]; hist_out [streams, hist_bins] float64, delays_out
+    [streams, hops, 8] float64 and n_peaks [streams, hops] int32, contiguous."""
+    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or \
+            mix.stride(2) != 1 or not mix.is_cuda:
+        raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
+    streams, _, n = mix.shape
+    if n == 0 or n % plan.hop:
+        raise ValueError("mix must hold a whole number (>= 1) of hops")
+    hops = n // plan.hop
+    if mask is None:
+        mask = torch.ones((streams, plan.F, hops), dtype=torch.float32, device=mix.device)
+    if tuple(mask.shape) != (streams, plan.F, hops) or mask.dtype != torch.float32 or \
+            mask.device != mix.device:
+        raise ValueError("mask must be float32 [streams, F, hops] on the mixture's device")
+    if angles is not None and (angles.dtype != torch.float64 or tuple(angles.shape) != (streams,)
+                               or not angles.is_contiguous() or angles.device != mix.device):
+        raise ValueError("angles must be a contiguous float64 [streams] tensor on the device")
+    a = _lib.AvzDelayStreamArgs()
+    a.streams, a.hops, a.forget = streams, hops, float(forget)
+    a.active, a.adapt = _ptr(active), _ptr(adapt)
+    a.mix, a.mix_stride, a.ch_stride = _ptr(mix), mix.stride(0), mix.stride(1)
+    a.angle_deg = _ptr(angles)
+    a.hist_bins, a.smooth, a.max_peaks = int(hist_bins), int(smooth), int(max_peaks)
+    a.rel_height, a.min_sep, a.f_lo_hz = float(rel_height), float(min_sep), float(f_lo)
+    a.mask = _ptr(mask)
+    a.mask_stride_b, a.mask_stride_f, a.mask_stride_t = mask.stride()
+    for name, t, shape, dt in (("hist_out", hist_out, (streams, int(hist_bins)), torch.float64),
+                               ("delays_out", delays_out, (streams, hops, 8), torch.float64),
+                               ("n_peaks", n_peaks, (streams, hops), torch.int32)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}")
+    a.hist_out, a.delays_out, a.n_peaks = _ptr(hist_out), _ptr(delays_out), _ptr(n_peaks)
+    a.state, a.state_bytes = _ptr(state), state.numel()
+    with torch.cuda.device(mix.device):
+        check(lib.avz_delay_stream_push(plan._h, ct.byref(a), _stream_handle(stream)),
+              "avz_delay_stream_push")
+    return mask
+
+
 def srp_scan(plan: MVDRPlan, mix: torch.Tensor, lengths=None, max_len=None, n_angles=181,
              angle_lo=0.0, angle_hi=180.0, f_lo=200.0, f_hi=4000.0, stream=None):
     """scripts/debug_srp.py:46-62 for a [B, 2, S] batch -> power map [B, n_angles] in dB

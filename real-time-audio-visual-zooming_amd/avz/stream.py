@@ -4,7 +4,10 @@
 (include/avz.h) over one caller-owned device state buffer; ``NumpyStream`` / ``stream_numpy``
 restate the algorithm in fp64 (the tests' reference, DESIGN.md section 13);
 ``enhance_stream`` runs a whole file through the device path and trims the one-hop delay:
-the causal counterpart of oracle_debug.enhance / process_chunk.
+the causal counterpart of oracle_debug.enhance / process_chunk. ``StreamingDelayMask`` drives
+avz_delay_stream_push, the streaming blind delay-histogram mask (DESIGN.md section 19);
+``StreamingBlindBeamformer`` feeds its mask to a ``StreamingBeamformer`` and
+``enhance_blind_stream`` runs a whole file through the pair: no references, no model.
 
 The algorithm, with H = N / 2 and x_t the t-th pushed hop (x_-1 = 0): frame t = [x_t-1 | x_t]
 under the fp32 periodic Hann scaled by 1 / sum(w) (frame t of scipy.signal.stft); the noise
@@ -325,3 +328,151 @@ def enhance_stream(y_mix, mask_fn_or_refs=None, hops_per_push: int = 1, *, n_fft
         outs.append(sb.push(x[:, :, sl].contiguous(), **kw))
     outs.append(sb.flush())
     return torch.cat(outs, dim=1)[0, H:H + L].cpu().numpy()
+
+
+# ---------------------------------------------------------------------------- blind device path
+class StreamingDelayMask:
+    """`streams` independent streaming blind delay-histogram masks over one device state buffer
+    (avz_delay_stream_push, include/avz.h). The plan supplies n_fft, fs,
+    mic_d, c_sound, angle_deg and max_batch; its mask and beamformer settings play no part.
+    mask_kw: smooth, rel_height, min_sep, max_peaks, f_lo (avz_delay_mask's). After a push
+    self.hist [streams, hist_bins] holds h after its last frame, self.delays [streams, hops, 8]
+    and self.n_peaks [streams, hops] every frame's list."""
+
+    def __init__(self, plan, streams: int, hist_bins: int = 65, forget: float = 1.0, device=None,
+                 **mask_kw):
+        import torch
+        from . import engine
+        from .delay_mask import DEFAULTS
+        unknown = set(mask_kw) - (set(DEFAULTS) - {"hist_bins"})
+        if unknown:
+            raise TypeError(f"unknown mask options {sorted(unknown)}")
+        self.plan, self.streams, self.forget = plan, int(streams), float(forget)
+        self.hist_bins, self.mask_kw = int(hist_bins), dict(mask_kw)
+        self.device = torch.device(device if device is not None else "cuda")
+        nbytes = engine.delay_stream_state_bytes(plan, self.streams, self.hist_bins)
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.hist = torch.zeros((self.streams, self.hist_bins), dtype=torch.float64,
+                                device=self.device)
+        self.angles = None
+        self.delays = self.n_peaks = None
+        self.reset()
+
+    _flags = StreamingBeamformer._flags
+
+    def reset(self, select=None, stream=None):
+        """Start the selected streams (flags per stream; None = all) afresh: zero history and
+        histogram. The target azimuths stay."""
+        from . import engine
+        engine.delay_stream_reset(self.plan, self.state, self.streams, self.hist_bins,
+                                  self._flags(select, "select"), stream)
+
+    def steer(self, angles):
+        """New target azimuth per stream in degrees (NaN = the plan's), from the next pushed
+        frame; None returns every stream to the plan's."""
+        import torch
+        if angles is None:
+            self.angles = None
+            return
+        a = torch.as_tensor(angles, dtype=torch.float64).to(self.device).contiguous()
+        if tuple(a.shape) != (self.streams,):
+            raise ValueError("angles must have one entry per stream")
+        self.angles = a
+
+    def push(self, mix, *, active=None, adapt=None, mask=None, stream=None):
+        """mix [streams, 2, hops * hop] float32 -> mask [streams, F, hops] float32: column j
+        labels the frame that ends with hop j, the frame StreamingBeamformer.push of the same
+        hops weights."""
+        import torch
+        from . import engine
+        if mix.dim() != 3 or mix.shape[0] != self.streams:
+            raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
+        hops = mix.shape[2] // self.plan.hop
+        self.delays = torch.full((self.streams, hops, 8), float("nan"), dtype=torch.float64,
+                                 device=mix.device)
+        self.n_peaks = torch.zeros((self.streams, hops), dtype=torch.int32, device=mix.device)
+        return engine.delay_stream_push(self.plan, self.state, mix, mask, forget=self.forget,
+                                        angles=self.angles, active=self._flags(active, "active"),
+                                        adapt=self._flags(adapt, "adapt"),
+                                        hist_bins=self.hist_bins, hist_out=self.hist,
+                                        delays_out=self.delays, n_peaks=self.n_peaks,
+                                        stream=stream, **self.mask_kw)
+
+
+class StreamingBlindBeamformer:
+    """A StreamingDelayMask feeding a StreamingBeamformer on an external-mask plan: causal
+    blind enhancement from two microphones and an angle per stream. push() is the mask, then
+    the beamformer, on the same hops; out is one hop behind the input. self.mask holds the
+    last push's mask."""
+
+    def __init__(self, plan, streams: int, forget: float = 0.99, hist_bins: int = 65,
+                 hist_forget: float = 1.0, device=None, **mask_kw):
+        if plan.cfg.mask != "external":
+            raise ValueError("StreamingBlindBeamformer needs a plan with mask='external'")
+        self.plan, self.streams = plan, int(streams)
+        self.masker = StreamingDelayMask(plan, streams, hist_bins, hist_forget, device, **mask_kw)
+        self.beamformer = StreamingBeamformer(plan, streams, forget, device)
+        self.mask = None
+
+    def reset(self, select=None, stream=None):
+        self.masker.reset(select, stream)
+        self.beamformer.reset(select, stream)
+
+    def steer(self, angles, stream=None):
+        """New target azimuth per stream in degrees, for the mask's anchor and the beamformer's
+        steering vector alike. A NaN entry keeps the beamformer's direction and returns the
+        mask's anchor to the plan's angle."""
+        self.masker.steer(angles)
+        self.beamformer.steer(angles, stream)
+
+    def push(self, mix, *, active=None, adapt=None, out=None, stream=None):
+        self.mask = self.masker.push(mix, active=active, adapt=adapt, stream=stream)
+        return self.beamformer.push(mix, mask=self.mask, active=active, adapt=adapt, out=out,
+                                    stream=stream)
+
+    def flush(self, **kw):
+        """Push one hop of zeros through both: returns the last hop."""
+        import torch
+        z = torch.zeros((self.streams, 2, self.plan.hop), dtype=torch.float32,
+                        device=self.beamformer.device)
+        return self.push(z, **kw)
+
+
+def enhance_blind_stream(y_mix, hops_per_push: int = 1, dereverb: bool = False, *,
+                         n_fft: int = 1024, mic_d: float = 0.08, sigma: float = 1e-5,
+                         angle: float = 90.0, fs: int = 16000, c_sound: float = 343.0,
+                         pf_floor: float = 0.05, forget: float = 0.99, hist_forget: float = 1.0,
+                         wpe_kw=None, device="cuda", **mask_kw):
+    """The causal counterpart of delay_mask.enhance_blind: y_mix [2, L] float32 -> [L] float32
+    (not normalised), the file pushed ``hops_per_push`` hops at a time through
+    StreamingBlindBeamformer (external mask, floor post-filter), drained, the one-hop delay
+    trimmed. ``dereverb``: dereverb.StreamingWPE (options ``wpe_kw``) in front, two hops of
+    delay in all. forget: the beamformer's; hist_forget: the histogram's. mask_kw:
+    hist_bins, smooth, rel_height, min_sep, max_peaks, f_lo."""
+    import torch
+    from .engine import MVDRPlan
+    y = np.ascontiguousarray(y_mix, dtype=np.float32)
+    if y.ndim != 2 or y.shape[0] != 2 or y.shape[1] < 1:
+        raise ValueError("y_mix must be (2, L) samples")
+    L, H = y.shape[1], n_fft // 2
+    T = -(-L // H)
+    plan = MVDRPlan(n_fft=n_fft, fs=fs, sigma=sigma, mic_d=mic_d, c_sound=c_sound,
+                    angle_deg=angle, mask="external", postfilter="floor", pf_floor=pf_floor,
+                    normalize="none", max_batch=1, max_samples=max(T * H, n_fft))
+    dev = torch.device(device)
+    x = torch.from_numpy(np.pad(y, [(0, 0), (0, T * H - L)]))[None].to(dev)
+    hist_bins = mask_kw.pop("hist_bins", 65)
+    bb = StreamingBlindBeamformer(plan, 1, forget, hist_bins, hist_forget, dev, **mask_kw)
+    sw = None
+    if dereverb:
+        from .dereverb import StreamingWPE
+        sw = StreamingWPE(plan, 1, device=dev, **(wpe_kw or {}))
+    outs = []
+    for j0 in range(0, T, hops_per_push):
+        blk = x[:, :, j0 * H:min(j0 + hops_per_push, T) * H].contiguous()
+        outs.append(bb.push(sw.push(blk) if sw else blk))
+    if sw:
+        outs.append(bb.push(sw.flush()))
+    outs.append(bb.flush())
+    lag = 2 * H if sw else H
+    return torch.cat(outs, dim=1)[0, lag:lag + L].cpu().numpy()

@@ -16,6 +16,7 @@
 #include "../../include/avz.h"
 #include "avz_internal.h"
 #include "avz_delay_mask.hpp"
+#include "avz_delay_stream.hpp"
 
 // Per-call device workspace of the chain (see avz_internal.h ChainArgs), carved from one
 // caller-provided block (avz_mvdr_workspace_bytes) or from the plan's own arena.
@@ -1663,6 +1664,156 @@ extern "C" int avz_delay_mask(const avz_plan* p, const avz_delay_mask_args* a, v
   k.list = reinterpret_cast<double*>(ws + lay.list_off);
   k.count = reinterpret_cast<int*>(ws + lay.count_off);
   rc = avz_launch_delay_mask(N, &k, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+// ------------------------------------------------------------------ streaming blind delay mask
+// As avz_delay_mask and the streaming entry points: every check runs on the host before any HIP
+// call, and avz_delay_stream_check takes the configuration itself (tests without a device).
+static int delay_stream_state_check(const avz_config& c, const void* state, long long state_bytes,
+                                    int streams, int hist_bins) {
+  if (!state) return AVZ_ERR_ARG;
+  if (streams < 1 || streams > c.max_batch) return AVZ_ERR_SHAPE;
+  if (state_bytes < avz::DelayStreamLayout(c.n_fft, hist_bins).stride * streams)
+    return AVZ_ERR_SHAPE;
+  if (misaligned(state, 256)) return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+extern "C" int avz_delay_stream_check(const avz_config* cfg, const avz_delay_stream_args* a) {
+  if (!cfg || !a) return AVZ_ERR_ARG;
+  const avz_config& c = *cfg;
+  if (!a->mix || !a->mask || !a->state) return AVZ_ERR_ARG;
+  if (a->hops < 1) return AVZ_ERR_ARG;
+  if (!(a->forget > 0.0 && a->forget <= 1.0)) return AVZ_ERR_ARG;  // NaN included
+  int rc = delay_param_check(a->hist_bins);
+  if (rc != AVZ_OK) return rc;
+  if (a->smooth < 0 || a->smooth > 8 || a->max_peaks < 0 ||
+      a->max_peaks > avz::kDelayStreamList - 1)
+    return AVZ_ERR_ARG;
+  if (!(a->rel_height > 0.0 && a->rel_height <= 1.0)) return AVZ_ERR_ARG;  // NaN included
+  if (!(a->min_sep >= 0.0) || !(a->f_lo_hz >= 0.0)) return AVZ_ERR_ARG;
+  if (a->streams < 1 || a->streams > c.max_batch) return AVZ_ERR_SHAPE;
+  const long long row = (long long)a->hops * c.hop;
+  if (row > (1LL << 30)) return AVZ_ERR_SHAPE;
+  if (a->ch_stride < row) return AVZ_ERR_SHAPE;
+  if (a->streams > 1 && a->mix_stride < a->ch_stride + row) return AVZ_ERR_SHAPE;
+  const long long T = a->hops, F = c.n_fft / 2 + 1;
+  const long long sf = a->mask_stride_f, st = a->mask_stride_t;
+  if (sf < 1 || st < 1) return AVZ_ERR_SHAPE;
+  const bool t_fastest = sf >= T * st, f_fastest = st >= F * sf;
+  if (!t_fastest && !f_fastest) return AVZ_ERR_SHAPE;
+  if (a->streams > 1 && a->mask_stride_b < (t_fastest ? F * sf : T * st)) return AVZ_ERR_SHAPE;
+  rc = delay_stream_state_check(c, a->state, a->state_bytes, a->streams, a->hist_bins);
+  if (rc != AVZ_OK) return rc;
+  if (misaligned(a->mix, 4) || misaligned(a->mask, 4) || misaligned(a->active, 4) ||
+      misaligned(a->adapt, 4) || misaligned(a->angle_deg, 8) || misaligned(a->hist_out, 8) ||
+      misaligned(a->delays_out, 8) || misaligned(a->n_peaks, 4))
+    return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+// hist_bins and n_fft of every state buffer reset in this process, by address: what lets a push
+// be refused on the host, the device header unread.
+namespace {
+struct DelayStreamRecord {
+  int hist_bins, n_fft;
+};
+std::mutex g_delay_stream_mu;
+std::unordered_map<const void*, DelayStreamRecord> g_delay_stream_rec;
+}  // namespace
+
+extern "C" long long avz_delay_stream_state_bytes(const avz_plan* p, int streams, int hist_bins) {
+  if (!p) return AVZ_ERR_ARG;
+  const int rc = delay_param_check(hist_bins);
+  if (rc != AVZ_OK) return rc;
+  if (streams < 1 || streams > p->cfg.max_batch) return AVZ_ERR_SHAPE;
+  return avz::DelayStreamLayout(p->cfg.n_fft, hist_bins).stride * streams;
+}
+
+extern "C" int avz_delay_stream_reset(const avz_plan* p, void* state, long long state_bytes,
+                                      int streams, int hist_bins, const int* select,
+                                      void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = delay_param_check(hist_bins);
+  if (rc != AVZ_OK) return rc;
+  rc = delay_stream_state_check(p->cfg, state, state_bytes, streams, hist_bins);
+  if (rc != AVZ_OK) return rc;
+  if (misaligned(select, 4)) return AVZ_ERR_ALIGN;
+  const DelayStreamRecord now{hist_bins, p->cfg.n_fft};
+  {
+    // a partial reset may not change what the other streams of the buffer were laid out for
+    std::lock_guard<std::mutex> lock(g_delay_stream_mu);
+    auto it = g_delay_stream_rec.find(state);
+    if (select && (it == g_delay_stream_rec.end() || it->second.hist_bins != hist_bins ||
+                   it->second.n_fft != now.n_fft))
+      return AVZ_ERR_ARG;
+    g_delay_stream_rec[state] = now;
+  }
+  avz::DelayStreamArgs s{};
+  s.streams = streams;
+  s.nb = hist_bins;
+  s.state = static_cast<unsigned char*>(state);
+  s.state_stride = avz::DelayStreamLayout(p->cfg.n_fft, hist_bins).stride;
+  s.select = select;
+  rc = avz_launch_delay_stream_reset(p->cfg.n_fft, &s, stream);
+  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
+  return rc;
+}
+
+extern "C" int avz_delay_stream_push(const avz_plan* p, const avz_delay_stream_args* a,
+                                     void* stream) {
+  if (!p) return AVZ_ERR_ARG;
+  int rc = avz_delay_stream_check(&p->cfg, a);
+  if (rc != AVZ_OK) return rc;
+  const avz_config& c = p->cfg;
+  const int N = c.n_fft;
+  {
+    std::lock_guard<std::mutex> lock(g_delay_stream_mu);
+    auto it = g_delay_stream_rec.find(a->state);
+    if (it == g_delay_stream_rec.end() || it->second.hist_bins != a->hist_bins ||
+        it->second.n_fft != N)
+      return AVZ_ERR_ARG;
+  }
+  avz::DelayStreamArgs k{};
+  k.streams = a->streams;
+  k.hops = a->hops;
+  k.forget = a->forget;
+  k.active = a->active;
+  k.adapt = a->adapt;
+  k.mix = a->mix;
+  k.mix_stride = a->mix_stride;
+  k.ch_stride = a->ch_stride;
+  k.angle_deg = a->angle_deg;
+  k.plan_angle = c.angle_deg;
+  k.nb = a->hist_bins;
+  k.smooth = a->smooth;
+  k.max_peaks = a->max_peaks;
+  k.rel_height = a->rel_height;
+  k.min_sep = a->min_sep;
+  // avz_delay_mask's grid
+  k.dmax = c.mic_d * (double)c.fs / c.c_sound;
+  k.R = 1.25 * k.dmax;
+  k.bin_w = 2.0 * k.R / a->hist_bins;
+  const double lo = std::ceil(a->f_lo_hz * N / (double)c.fs);
+  k.k_lo = lo >= N ? N : std::max(1, (int)lo);  // above N / 2: an empty band
+  k.k_hi = -1;  // empty band: no spacing, no delay to find
+  if (k.R > 0.0 && std::isfinite(k.R)) {
+    const double lim = std::ceil(N / (2.0 * k.R)) - 1.0;  // largest k with omega_k R < pi
+    k.k_hi = lim >= N / 2 ? N / 2 : (int)lim;
+  }
+  k.mask = a->mask;
+  k.m_sb = a->mask_stride_b;
+  k.m_sf = a->mask_stride_f;
+  k.m_st = a->mask_stride_t;
+  k.hist_out = a->hist_out;
+  k.delays_out = a->delays_out;
+  k.n_peaks = a->n_peaks;
+  k.state = static_cast<unsigned char*>(a->state);
+  k.state_stride = avz::DelayStreamLayout(N, a->hist_bins).stride;
+  k.xwin = p->xwin;
+  rc = avz_launch_delay_stream_push(N, &k, stream);
   if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
   return rc;
 }
