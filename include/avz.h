@@ -136,7 +136,11 @@ typedef struct avz_batch_args {
   const float* ref_tgt;    /* [batch][ref_stride] target reference (IBM) or NULL                */
   const float* ref_int;    /* [batch][ref_stride] interference reference (IBM) or NULL          */
   long long ref_stride;
-  const float* ext_mask;   /* target probability M[b][k][t] (EXTERNAL) or NULL                   */
+  const float* ext_mask;   /* target probability M[b][k][t] (EXTERNAL) or NULL. Only k < F and
+                              t < frames(len[b]) of row b are used: entries at later frames, row
+                              padding between the strides and bins >= F never influence an
+                              output. Strides in floats, any layout; mask_stride_b = 0 (one
+                              mask for the whole batch) is allowed                             */
   long long mask_stride_b, mask_stride_f, mask_stride_t;
   float* out;              /* [batch][out_stride], out_stride % 4 == 0, 16-byte aligned          */
   long long out_stride;
@@ -174,7 +178,9 @@ long long avz_mvdr_workspace_bytes(const avz_plan* plan, int batch, int max_len)
  *                       plan's own buffer, calls then serialised).
  *  avz_apply_istft      STFT of args->mix -> S = w^H y (x args->ext_mask as a gain when
  *                       non-NULL, mask_bins / mask_frames as for EXTERNAL) -> iSTFT/OLA ->
- *                       args->out (peak-normalised per the plan), args->peak.
+ *                       args->out (peak-normalised per the plan), args->peak. The gain is
+ *                       applied as given: no clamp to [0, 1], no floor (the plan's
+ *                       post-filter and pf_floor play no part here).
  * Device arrays; the same workspace rules as avz_mvdr_batch. */
 int avz_mvdr_covariance(const avz_plan* plan, const avz_batch_args* args, void* hip_stream);
 int avz_solve_covariance(const avz_plan* plan, int batch, const double* cov, float* w,
@@ -249,7 +255,10 @@ int avz_wpe_spectral(const avz_wpe_args* args, void* hip_stream);
 /* scipy.signal.istft(S, fs, nperseg=n_fft, noverlap=n_fft/2) of complex64 S[b][k][t]
  * (t contiguous; strides in complex elements) for `frames` frames per item: out[b] gets
  * (frames - 1) * hop samples (<= max_samples), peak-normalised per the plan; peak[b] =
- * max|out| before normalisation (or NULL). The same workspace rules as avz_mvdr_batch
+ * max|out| before normalisation (or NULL). frames >= 3: (frames - 1) * hop < n_fft, which
+ * scipy accepts (two frames), returns AVZ_ERR_SHAPE, as a time-domain row shorter than a frame
+ * is not processed. The imaginary parts of the DC and Nyquist bins are ignored (as irfft
+ * ignores them). The same workspace rules as avz_mvdr_batch
  * (workspace bytes: avz_mvdr_workspace_bytes(plan, batch, (frames - 1) * hop)). Replaces
  * the istft calls at oracle_debug.py:93, tf_lite_version/inference.py:352,
  * Final_pipeline/src/inference.py:222. */

@@ -199,11 +199,23 @@ __device__ __forceinline__ void synthesis_item(const ChainArgs& A, unsigned char
           ga = gain(bits[j], ia, ta, kb);
           gb = gain(bits[j], ia + 1, ta + 1, kb);
         }
-        const cf sa = apply_bin(alpha[j], beta[j], za[p], zap[p], ga);
-        const cf sb = apply_bin(alpha[j], beta[j], zb[p], zbp[p], gb);
-        Za[kp] = {sa.x + sb.y, sb.x - sa.y};  // conj(Sa) + i conj(Sb) at N - k
-        // Sa + i Sb at k; at DC irfft keeps only the real parts (written last: kp == kb)
-        Za[kb] = (kb == 0) ? cf{sa.x, sb.x} : cf{sa.x - sb.y, sa.y + sb.x};
+        if constexpr (PF == PF_EXT_FLOOR || PF == PF_EXT_MUL) {
+          // A gain from memory: the vector and the scalar instance of this phase must give
+          // the same bits whatever the mask's layout, so every rounding is spelled out (left
+          // to the compiler's contraction, the two instances differed at N = 1024 in how
+          // g s folds into the packing sums).
+          const cf ua = apply_sum_fma(alpha[j], beta[j], za[p], zap[p]);
+          const cf ub = apply_sum_fma(alpha[j], beta[j], zb[p], zbp[p]);
+          const float ax = ga * ua.x, ay = ga * ua.y;  // Sa = ga ua
+          Za[kp] = {fmaf(gb, ub.y, ax), fmaf(gb, ub.x, -ay)};  // as below, Sb = gb ub
+          Za[kb] = (kb == 0) ? cf{ax, gb * ub.x} : cf{fmaf(-gb, ub.y, ax), fmaf(gb, ub.x, ay)};
+        } else {
+          const cf sa = apply_bin(alpha[j], beta[j], za[p], zap[p], ga);
+          const cf sb = apply_bin(alpha[j], beta[j], zb[p], zbp[p], gb);
+          Za[kp] = {sa.x + sb.y, sb.x - sa.y};  // conj(Sa) + i conj(Sb) at N - k
+          // Sa + i Sb at k; at DC irfft keeps only the real parts (written last: kp == kb)
+          Za[kb] = (kb == 0) ? cf{sa.x, sb.x} : cf{sa.x - sb.y, sa.y + sb.x};
+        }
       }
     }
     };

@@ -460,6 +460,12 @@ __device__ __forceinline__ cf apply_bin(cf alpha, cf beta, cf z, cf zp, float g)
   const cf s = c_add(c_mul(alpha, z), c_mul(beta, c_conj(zp)));
   return {g * s.x, g * s.y};
 }
+// alpha z + beta conj(zp) with its roundings fixed (one product, three fused steps per part):
+// for callers whose instances must agree bitwise (avz_chain_synthesis.hpp, gains from memory).
+__device__ __forceinline__ cf apply_sum_fma(cf alpha, cf beta, cf z, cf zp) {
+  return {fmaf(alpha.x, z.x, fmaf(-alpha.y, z.y, fmaf(beta.x, zp.x, beta.y * zp.y))),
+          fmaf(alpha.x, z.y, fmaf(alpha.y, z.x, fmaf(beta.y, zp.x, -(beta.x * zp.y))))};
+}
 
 
 // ---- host side

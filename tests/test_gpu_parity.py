@@ -239,8 +239,10 @@ def test_fused_external_mask(avz, gpu_device, n, floor):
     torch.cuda.synchronize()
     got2 = out2[0, :len(ref)].cpu().numpy()
     assert np.max(np.abs(got2 - ref)) <= WAVE_TOL * scale
-    # t-contiguous rows padded to a multiple of 4 frames (16-B aligned row starts) while T
-    # itself is not: 16-B row-segment reads on the full steps, scalar reads on the last
+    # t-contiguous rows padded to a multiple of 4 frames (16-B aligned row starts): 16-B
+    # row-segment reads on the full 8-frame steps. N = 512 (T = 126) ends in a partial step
+    # read by scalars; at N = 1024 (T = 64) every step is full, so no scalar read follows the
+    # vector ones here (tests/test_gpu_gain_paths.py runs that case)
     T = M.shape[1]
     Mp = np.zeros((M.shape[0], -(-T // 4) * 4), np.float32)
     Mp[:, :T] = M
