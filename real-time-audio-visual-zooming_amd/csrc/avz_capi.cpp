@@ -1283,6 +1283,69 @@ extern "C" int avz_projection_metrics(int batch, int max_len, const int* len, co
 // Every check below runs on the host from the plan's configuration alone, before any HIP
 // call. The avz_stream_check_* forms take the configuration itself, so they can be exercised
 // without a device (tests); the public entry points call them with the plan's.
+
+// A caller-owned state buffer of `streams` blocks of `stride` bytes.
+static int state_buffer_check(const void* state, long long state_bytes, int streams,
+                              int max_batch, long long stride) {
+  if (!state) return AVZ_ERR_ARG;
+  if (streams < 1 || streams > max_batch) return AVZ_ERR_SHAPE;
+  if (state_bytes < stride * streams) return AVZ_ERR_SHAPE;
+  if (misaligned(state, 256)) return AVZ_ERR_ALIGN;
+  return AVZ_OK;
+}
+
+// n planar rows of `row` samples per channel: mix[i * mix_stride + ch * ch_stride + ..].
+static int planar_rows_check(long long row, int n, long long ch_stride, long long mix_stride) {
+  if (ch_stride < row) return AVZ_ERR_SHAPE;
+  if (n > 1 && mix_stride < ch_stride + row) return AVZ_ERR_SHAPE;
+  return AVZ_OK;
+}
+
+// The rows a push call brings: `hops` hops per channel, *row samples.
+static int pushed_rows_check(int hops, double forget, int hop, int streams, long long ch_stride,
+                             long long mix_stride, long long* row) {
+  if (hops < 1) return AVZ_ERR_ARG;
+  if (!(forget > 0.0 && forget <= 1.0)) return AVZ_ERR_ARG;  // NaN included
+  *row = (long long)hops * hop;
+  if (*row > (1LL << 30)) return AVZ_ERR_SHAPE;
+  return planar_rows_check(*row, streams, ch_stride, mix_stride);
+}
+
+// A mask M[b * sb + k * sf + t * st] of F bins and T frames: either index may run fastest, the
+// rows may be padded, none may overlap.
+static int mask_stride_check(long long T, long long F, long long sb, long long sf, long long st,
+                             int batch) {
+  if (sf < 1 || st < 1) return AVZ_ERR_SHAPE;
+  const bool t_fastest = sf >= T * st, f_fastest = st >= F * sf;
+  if (!t_fastest && !f_fastest) return AVZ_ERR_SHAPE;
+  if (batch > 1 && sb < (t_fastest ? F * sf : T * st)) return AVZ_ERR_SHAPE;
+  return AVZ_OK;
+}
+
+// What every state buffer reset in this process was laid out for, by address: what lets a push
+// be refused on the host, the device header unread.
+template <class Record>
+class StateRegistry {
+  std::mutex mu_;
+  std::unordered_map<const void*, Record> rec_;
+
+ public:
+  bool matches(const void* state, const Record& r) {
+    std::lock_guard<std::mutex> lock(mu_);
+    auto it = rec_.find(state);
+    return it != rec_.end() && it->second == r;
+  }
+  // A reset. A partial one may not change what the other streams of the buffer were laid out
+  // for: it is refused (false) on a buffer that is unknown or has another layout.
+  bool record(const void* state, const Record& r, bool partial) {
+    std::lock_guard<std::mutex> lock(mu_);
+    auto it = rec_.find(state);
+    if (partial && (it == rec_.end() || !(it->second == r))) return false;
+    rec_[state] = r;
+    return true;
+  }
+};
+
 static int stream_config_check(const avz_config& c) {
   if (c.beamformer != AVZ_BF_MVDR || c.mask_mode == AVZ_MASK_IPD ||
       c.postfilter == AVZ_PF_IRM || c.singular_fallback == AVZ_FALLBACK_BATCH ||
@@ -1304,11 +1367,8 @@ static int stream_state_check(const avz_config& c, const void* state, long long 
                               int streams) {
   const int rc = stream_config_check(c);
   if (rc != AVZ_OK) return rc;
-  if (!state) return AVZ_ERR_ARG;
-  if (streams < 1 || streams > c.max_batch) return AVZ_ERR_SHAPE;
-  if (state_bytes < avz::StreamLayout(c.n_fft).stride * streams) return AVZ_ERR_SHAPE;
-  if (misaligned(state, 256)) return AVZ_ERR_ALIGN;
-  return AVZ_OK;
+  return state_buffer_check(state, state_bytes, streams, c.max_batch,
+                            avz::StreamLayout(c.n_fft).stride);
 }
 
 extern "C" int avz_stream_check_state(const avz_config* c, const void* state,
@@ -1329,15 +1389,12 @@ extern "C" int avz_stream_check_push(const avz_config* cfg, const avz_stream_arg
   if (!a->mix || !a->out || !a->state) return AVZ_ERR_ARG;
   if (c.mask_mode == AVZ_MASK_IBM && (!a->ref_tgt || !a->ref_int)) return AVZ_ERR_ARG;
   if (c.mask_mode == AVZ_MASK_EXTERNAL && !a->ext_mask) return AVZ_ERR_ARG;
-  if (a->hops < 1) return AVZ_ERR_ARG;
-  if (!(a->forget > 0.0 && a->forget <= 1.0)) return AVZ_ERR_ARG;  // NaN included
-  if (a->streams < 1 || a->streams > c.max_batch) return AVZ_ERR_SHAPE;
-  const long long row = (long long)a->hops * c.hop;
-  if (row > (1LL << 30)) return AVZ_ERR_SHAPE;
-  if (a->ch_stride < row || a->out_stride < row) return AVZ_ERR_SHAPE;
-  if (a->streams > 1 && a->mix_stride < a->ch_stride + row) return AVZ_ERR_SHAPE;
+  long long row;
+  rc = pushed_rows_check(a->hops, a->forget, c.hop, a->streams, a->ch_stride, a->mix_stride, &row);
+  if (rc != AVZ_OK) return rc;
+  if (a->out_stride < row) return AVZ_ERR_SHAPE;
   if (c.mask_mode == AVZ_MASK_IBM && a->streams > 1 && a->ref_stride < row) return AVZ_ERR_SHAPE;
-  rc = stream_state_check(c, a->state, a->state_bytes, a->streams);
+  rc = stream_state_check(c, a->state, a->state_bytes, a->streams);  // streams' range too
   if (rc != AVZ_OK) return rc;
   if (misaligned(a->out, 16) || (a->out_stride & 3)) return AVZ_ERR_ALIGN;
   if (misaligned(a->mix, 4) || misaligned(a->ref_tgt, 4) || misaligned(a->ref_int, 4) ||
@@ -1362,9 +1419,7 @@ extern "C" int avz_stream_reset(const avz_plan* p, void* state, long long state_
   s.state = static_cast<unsigned char*>(state);
   s.state_stride = avz::StreamLayout(p->cfg.n_fft).stride;
   s.select = select;
-  rc = avz_launch_stream_reset(p->cfg.n_fft, &s, p->steer, stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_stream_reset(p->cfg.n_fft, &s, p->steer, stream));
 }
 
 extern "C" int avz_stream_steer(const avz_plan* p, void* state, long long state_bytes,
@@ -1378,10 +1433,8 @@ extern "C" int avz_stream_steer(const avz_plan* p, void* state, long long state_
   s.state = static_cast<unsigned char*>(state);
   s.state_stride = avz::StreamLayout(p->cfg.n_fft).stride;
   s.angle_deg = angle_deg;
-  rc = avz_launch_stream_steer(p->cfg.n_fft, &s, p->cfg.mic_d, p->cfg.c_sound, (double)p->cfg.fs,
-                               stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_stream_steer(p->cfg.n_fft, &s, p->cfg.mic_d, p->cfg.c_sound,
+                                        (double)p->cfg.fs, stream));
 }
 
 extern "C" int avz_stream_push(const avz_plan* p, const avz_stream_args* a, void* stream) {
@@ -1414,9 +1467,7 @@ extern "C" int avz_stream_push(const avz_plan* p, const avz_stream_args* a, void
   s.mask_out = a->mask_out;
   s.state = static_cast<unsigned char*>(a->state);
   s.state_stride = avz::StreamLayout(c.n_fft).stride;
-  rc = avz_launch_stream_push(c.n_fft, c.mask_mode, &s, &k, stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_stream_push(c.n_fft, c.mask_mode, &s, &k, stream));
 }
 
 // ------------------------------------------------------------------ streaming online WPE
@@ -1438,12 +1489,8 @@ extern "C" long long avz_wpe_stream_check_state_bytes(const avz_config* c, int s
 
 static int wpe_stream_state_check(const avz_config& c, const void* state, long long state_bytes,
                                   int streams, int taps, int delay) {
-  if (!state) return AVZ_ERR_ARG;
-  if (streams < 1 || streams > c.max_batch) return AVZ_ERR_SHAPE;
-  if (state_bytes < avz::WpeStreamLayout(c.n_fft, taps, delay).stride * streams)
-    return AVZ_ERR_SHAPE;
-  if (misaligned(state, 256)) return AVZ_ERR_ALIGN;
-  return AVZ_OK;
+  return state_buffer_check(state, state_bytes, streams, c.max_batch,
+                            avz::WpeStreamLayout(c.n_fft, taps, delay).stride);
 }
 
 extern "C" int avz_wpe_stream_check_reset(const avz_config* c, const void* state,
@@ -1462,16 +1509,12 @@ extern "C" int avz_wpe_stream_check_push(const avz_config* cfg, const avz_wpe_st
   if (!a->mix || !a->out || !a->state) return AVZ_ERR_ARG;
   int rc = wpe_stream_param_check(a->taps, a->delay);
   if (rc != AVZ_OK) return rc;
-  if (!(a->forget > 0.0 && a->forget <= 1.0)) return AVZ_ERR_ARG;  // NaN included
   if (!(a->power_floor > 0.0) || !std::isfinite(a->power_floor)) return AVZ_ERR_ARG;
-  if (a->hops < 1) return AVZ_ERR_ARG;
-  if (a->streams < 1 || a->streams > c.max_batch) return AVZ_ERR_SHAPE;
-  const long long row = (long long)a->hops * c.hop;
-  if (row > (1LL << 30)) return AVZ_ERR_SHAPE;
-  if (a->ch_stride < row || a->out_ch_stride < row) return AVZ_ERR_SHAPE;
-  if (a->streams > 1 &&
-      (a->mix_stride < a->ch_stride + row || a->out_stride < a->out_ch_stride + row))
-    return AVZ_ERR_SHAPE;
+  long long row;
+  rc = pushed_rows_check(a->hops, a->forget, c.hop, a->streams, a->ch_stride, a->mix_stride, &row);
+  if (rc != AVZ_OK) return rc;
+  rc = planar_rows_check(row, a->streams, a->out_ch_stride, a->out_stride);
+  if (rc != AVZ_OK) return rc;
   rc = wpe_stream_state_check(c, a->state, a->state_bytes, a->streams, a->taps, a->delay);
   if (rc != AVZ_OK) return rc;
   if (misaligned(a->out, 16) || (a->out_stride & 3) || (a->out_ch_stride & 3))
@@ -1482,14 +1525,14 @@ extern "C" int avz_wpe_stream_check_push(const avz_config* cfg, const avz_wpe_st
   return AVZ_OK;
 }
 
-// taps, delay and n_fft of every state buffer reset in this process, by address: what lets a
-// push be refused on the host, the device header unread.
 namespace {
 struct WpeStreamRecord {
   int taps, delay, n_fft;
+  bool operator==(const WpeStreamRecord& o) const {
+    return taps == o.taps && delay == o.delay && n_fft == o.n_fft;
+  }
 };
-std::mutex g_wpe_stream_mu;
-std::unordered_map<const void*, WpeStreamRecord> g_wpe_stream_rec;
+StateRegistry<WpeStreamRecord> g_wpe_states;
 }  // namespace
 
 extern "C" long long avz_wpe_stream_state_bytes(const avz_plan* p, int streams, int taps,
@@ -1504,16 +1547,8 @@ extern "C" int avz_wpe_stream_reset(const avz_plan* p, void* state, long long st
   if (!p) return AVZ_ERR_ARG;
   int rc = avz_wpe_stream_check_reset(&p->cfg, state, state_bytes, streams, taps, delay, q_init);
   if (rc != AVZ_OK) return rc;
-  const WpeStreamRecord now{taps, delay, p->cfg.n_fft};
-  {
-    // a partial reset may not change what the other streams of the buffer were laid out for
-    std::lock_guard<std::mutex> lock(g_wpe_stream_mu);
-    auto it = g_wpe_stream_rec.find(state);
-    if (select && (it == g_wpe_stream_rec.end() || it->second.taps != taps ||
-                   it->second.delay != delay || it->second.n_fft != now.n_fft))
-      return AVZ_ERR_ARG;
-    g_wpe_stream_rec[state] = now;
-  }
+  if (!g_wpe_states.record(state, {taps, delay, p->cfg.n_fft}, select != nullptr))
+    return AVZ_ERR_ARG;
   avz::WpeStreamArgs s{};
   s.streams = streams;
   s.taps = taps;
@@ -1522,9 +1557,7 @@ extern "C" int avz_wpe_stream_reset(const avz_plan* p, void* state, long long st
   s.state = static_cast<unsigned char*>(state);
   s.state_stride = avz::WpeStreamLayout(p->cfg.n_fft, taps, delay).stride;
   s.select = select;
-  rc = avz_launch_wpe_stream_reset(p->cfg.n_fft, &s, stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_wpe_stream_reset(p->cfg.n_fft, &s, stream));
 }
 
 extern "C" int avz_wpe_stream_push(const avz_plan* p, const avz_wpe_stream_args* a,
@@ -1533,13 +1566,7 @@ extern "C" int avz_wpe_stream_push(const avz_plan* p, const avz_wpe_stream_args*
   int rc = avz_wpe_stream_check_push(&p->cfg, a);
   if (rc != AVZ_OK) return rc;
   const avz_config& c = p->cfg;
-  {
-    std::lock_guard<std::mutex> lock(g_wpe_stream_mu);
-    auto it = g_wpe_stream_rec.find(a->state);
-    if (it == g_wpe_stream_rec.end() || it->second.taps != a->taps ||
-        it->second.delay != a->delay || it->second.n_fft != c.n_fft)
-      return AVZ_ERR_ARG;
-  }
+  if (!g_wpe_states.matches(a->state, {a->taps, a->delay, c.n_fft})) return AVZ_ERR_ARG;
   avz::WpeStreamArgs s{};
   s.streams = a->streams;
   s.hops = a->hops;
@@ -1561,9 +1588,7 @@ extern "C" int avz_wpe_stream_push(const avz_plan* p, const avz_wpe_stream_args*
   s.G_out = a->G_out;
   s.state = static_cast<unsigned char*>(a->state);
   s.state_stride = avz::WpeStreamLayout(c.n_fft, a->taps, a->delay).stride;
-  rc = avz_launch_wpe_stream_push(c.n_fft, &s, p->xwin, stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_wpe_stream_push(c.n_fft, &s, p->xwin, stream));
 }
 
 // ------------------------------------------------------------------ blind delay-histogram mask
@@ -1572,6 +1597,42 @@ extern "C" int avz_wpe_stream_push(const avz_plan* p, const avz_wpe_stream_args*
 static int delay_param_check(int hist_bins) {
   if (hist_bins < 9 || hist_bins > avz::kDelayMaxBins || !(hist_bins & 1)) return AVZ_ERR_ARG;
   return AVZ_OK;
+}
+
+// The grid and peak arguments of avz_delay_mask and avz_delay_stream_push.
+static int delay_args_check(int hist_bins, int smooth, int max_peaks, double rel_height,
+                            double min_sep, double f_lo_hz) {
+  const int rc = delay_param_check(hist_bins);
+  if (rc != AVZ_OK) return rc;
+  if (smooth < 0 || smooth > 8 || max_peaks < 0 || max_peaks > avz::kDelayList - 1)
+    return AVZ_ERR_ARG;
+  if (!(rel_height > 0.0 && rel_height <= 1.0)) return AVZ_ERR_ARG;  // NaN included
+  if (!(min_sep >= 0.0) || !(f_lo_hz >= 0.0)) return AVZ_ERR_ARG;
+  return AVZ_OK;
+}
+
+// Those arguments and the plan's geometry as the kernels take them.
+static avz::DelayParams delay_params(const avz_config& c, int hist_bins, int smooth, int max_peaks,
+                                     double rel_height, double min_sep, double f_lo_hz) {
+  const int N = c.n_fft;
+  avz::DelayParams k{};
+  k.nb = hist_bins;
+  k.smooth = smooth;
+  k.max_peaks = max_peaks;
+  k.rel_height = rel_height;
+  k.min_sep = min_sep;
+  k.dmax = c.mic_d * (double)c.fs / c.c_sound;
+  k.R = 1.25 * k.dmax;
+  k.bin_w = 2.0 * k.R / hist_bins;
+  const double lo = std::ceil(f_lo_hz * N / (double)c.fs);
+  k.k_lo = lo >= N ? N : std::max(1, (int)lo);  // above N / 2: an empty band
+  k.k_hi = -1;  // empty band: no spacing, no delay to find
+  if (k.R > 0.0 && std::isfinite(k.R)) {
+    const double lim = std::ceil(N / (2.0 * k.R)) - 1.0;  // largest k with omega_k R < pi
+    k.k_hi = lim >= N / 2 ? N / 2 : (int)lim;
+  }
+  k.plan_angle = c.angle_deg;
+  return k;
 }
 
 static long long delay_workspace_bytes(const avz_config& c, int batch, int max_len,
@@ -1593,22 +1654,16 @@ extern "C" int avz_delay_mask_check(const avz_config* cfg, const avz_delay_mask_
   if (!cfg || !a) return AVZ_ERR_ARG;
   const avz_config& c = *cfg;
   if (!a->len || !a->mix || !a->mask || !a->workspace) return AVZ_ERR_ARG;
-  int rc = delay_param_check(a->hist_bins);
+  int rc = delay_args_check(a->hist_bins, a->smooth, a->max_peaks, a->rel_height, a->min_sep,
+                            a->f_lo_hz);
   if (rc != AVZ_OK) return rc;
-  if (a->smooth < 0 || a->smooth > 8 || a->max_peaks < 0 || a->max_peaks > avz::kDelayList - 1)
-    return AVZ_ERR_ARG;
-  if (!(a->rel_height > 0.0 && a->rel_height <= 1.0)) return AVZ_ERR_ARG;  // NaN included
-  if (!(a->min_sep >= 0.0) || !(a->f_lo_hz >= 0.0)) return AVZ_ERR_ARG;
   if (a->batch < 1 || a->batch > c.max_batch) return AVZ_ERR_SHAPE;
   if (a->max_len < c.n_fft || a->max_len > c.max_samples) return AVZ_ERR_SHAPE;
-  if (a->ch_stride < a->max_len) return AVZ_ERR_SHAPE;
-  if (a->batch > 1 && a->mix_stride < a->ch_stride + a->max_len) return AVZ_ERR_SHAPE;
-  const long long T = frames_for(a->max_len, c.hop), F = c.n_fft / 2 + 1;
-  const long long sf = a->mask_stride_f, st = a->mask_stride_t;
-  if (sf < 1 || st < 1) return AVZ_ERR_SHAPE;
-  const bool t_fastest = sf >= T * st, f_fastest = st >= F * sf;
-  if (!t_fastest && !f_fastest) return AVZ_ERR_SHAPE;
-  if (a->batch > 1 && a->mask_stride_b < (t_fastest ? F * sf : T * st)) return AVZ_ERR_SHAPE;
+  rc = planar_rows_check(a->max_len, a->batch, a->ch_stride, a->mix_stride);
+  if (rc != AVZ_OK) return rc;
+  rc = mask_stride_check(frames_for(a->max_len, c.hop), c.n_fft / 2 + 1, a->mask_stride_b,
+                         a->mask_stride_f, a->mask_stride_t, a->batch);
+  if (rc != AVZ_OK) return rc;
   if (a->workspace_bytes < delay_workspace_bytes(c, a->batch, a->max_len, a->hist_bins))
     return AVZ_ERR_SHAPE;
   if (misaligned(a->workspace, 256)) return AVZ_ERR_ALIGN;
@@ -1624,7 +1679,6 @@ extern "C" int avz_delay_mask(const avz_plan* p, const avz_delay_mask_args* a, v
   int rc = avz_delay_mask_check(&p->cfg, a);
   if (rc != AVZ_OK) return rc;
   const avz_config& c = p->cfg;
-  const int N = c.n_fft;
   avz::DelayArgs k{};
   k.batch = a->batch;
   k.len = a->len;
@@ -1636,22 +1690,8 @@ extern "C" int avz_delay_mask(const avz_plan* p, const avz_delay_mask_args* a, v
   k.mix_stride = a->mix_stride;
   k.ch_stride = a->ch_stride;
   k.angle_deg = a->angle_deg;
-  k.plan_angle = c.angle_deg;
-  k.nb = a->hist_bins;
-  k.smooth = a->smooth;
-  k.max_peaks = a->max_peaks;
-  k.rel_height = a->rel_height;
-  k.min_sep = a->min_sep;
-  k.dmax = c.mic_d * (double)c.fs / c.c_sound;
-  k.R = 1.25 * k.dmax;
-  k.bin_w = 2.0 * k.R / a->hist_bins;
-  const double lo = std::ceil(a->f_lo_hz * N / (double)c.fs);
-  k.k_lo = lo >= N ? N : std::max(1, (int)lo);  // above N / 2: an empty band
-  k.k_hi = -1;  // empty band: no spacing, no delay to find
-  if (k.R > 0.0 && std::isfinite(k.R)) {
-    const double lim = std::ceil(N / (2.0 * k.R)) - 1.0;  // largest k with omega_k R < pi
-    k.k_hi = lim >= N / 2 ? N / 2 : (int)lim;
-  }
+  k.p = delay_params(c, a->hist_bins, a->smooth, a->max_peaks, a->rel_height, a->min_sep,
+                     a->f_lo_hz);
   k.mask = a->mask;
   k.m_sb = a->mask_stride_b;
   k.m_sf = a->mask_stride_f;
@@ -1663,9 +1703,7 @@ extern "C" int avz_delay_mask(const avz_plan* p, const avz_delay_mask_args* a, v
   k.part = reinterpret_cast<double*>(ws + lay.part_off);
   k.list = reinterpret_cast<double*>(ws + lay.list_off);
   k.count = reinterpret_cast<int*>(ws + lay.count_off);
-  rc = avz_launch_delay_mask(N, &k, stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_delay_mask(c.n_fft, &k, stream));
 }
 
 // ------------------------------------------------------------------ streaming blind delay mask
@@ -1673,38 +1711,24 @@ extern "C" int avz_delay_mask(const avz_plan* p, const avz_delay_mask_args* a, v
 // call, and avz_delay_stream_check takes the configuration itself (tests without a device).
 static int delay_stream_state_check(const avz_config& c, const void* state, long long state_bytes,
                                     int streams, int hist_bins) {
-  if (!state) return AVZ_ERR_ARG;
-  if (streams < 1 || streams > c.max_batch) return AVZ_ERR_SHAPE;
-  if (state_bytes < avz::DelayStreamLayout(c.n_fft, hist_bins).stride * streams)
-    return AVZ_ERR_SHAPE;
-  if (misaligned(state, 256)) return AVZ_ERR_ALIGN;
-  return AVZ_OK;
+  return state_buffer_check(state, state_bytes, streams, c.max_batch,
+                            avz::DelayStreamLayout(c.n_fft, hist_bins).stride);
 }
 
 extern "C" int avz_delay_stream_check(const avz_config* cfg, const avz_delay_stream_args* a) {
   if (!cfg || !a) return AVZ_ERR_ARG;
   const avz_config& c = *cfg;
   if (!a->mix || !a->mask || !a->state) return AVZ_ERR_ARG;
-  if (a->hops < 1) return AVZ_ERR_ARG;
-  if (!(a->forget > 0.0 && a->forget <= 1.0)) return AVZ_ERR_ARG;  // NaN included
-  int rc = delay_param_check(a->hist_bins);
+  int rc = delay_args_check(a->hist_bins, a->smooth, a->max_peaks, a->rel_height, a->min_sep,
+                            a->f_lo_hz);
   if (rc != AVZ_OK) return rc;
-  if (a->smooth < 0 || a->smooth > 8 || a->max_peaks < 0 ||
-      a->max_peaks > avz::kDelayStreamList - 1)
-    return AVZ_ERR_ARG;
-  if (!(a->rel_height > 0.0 && a->rel_height <= 1.0)) return AVZ_ERR_ARG;  // NaN included
-  if (!(a->min_sep >= 0.0) || !(a->f_lo_hz >= 0.0)) return AVZ_ERR_ARG;
-  if (a->streams < 1 || a->streams > c.max_batch) return AVZ_ERR_SHAPE;
-  const long long row = (long long)a->hops * c.hop;
-  if (row > (1LL << 30)) return AVZ_ERR_SHAPE;
-  if (a->ch_stride < row) return AVZ_ERR_SHAPE;
-  if (a->streams > 1 && a->mix_stride < a->ch_stride + row) return AVZ_ERR_SHAPE;
-  const long long T = a->hops, F = c.n_fft / 2 + 1;
-  const long long sf = a->mask_stride_f, st = a->mask_stride_t;
-  if (sf < 1 || st < 1) return AVZ_ERR_SHAPE;
-  const bool t_fastest = sf >= T * st, f_fastest = st >= F * sf;
-  if (!t_fastest && !f_fastest) return AVZ_ERR_SHAPE;
-  if (a->streams > 1 && a->mask_stride_b < (t_fastest ? F * sf : T * st)) return AVZ_ERR_SHAPE;
+  long long row;
+  rc = pushed_rows_check(a->hops, a->forget, c.hop, a->streams, a->ch_stride, a->mix_stride, &row);
+  if (rc != AVZ_OK) return rc;
+  rc = mask_stride_check(a->hops, c.n_fft / 2 + 1, a->mask_stride_b, a->mask_stride_f,
+                         a->mask_stride_t, a->streams);
+  if (rc != AVZ_OK) return rc;
+  // (the streams' range too)
   rc = delay_stream_state_check(c, a->state, a->state_bytes, a->streams, a->hist_bins);
   if (rc != AVZ_OK) return rc;
   if (misaligned(a->mix, 4) || misaligned(a->mask, 4) || misaligned(a->active, 4) ||
@@ -1714,14 +1738,14 @@ extern "C" int avz_delay_stream_check(const avz_config* cfg, const avz_delay_str
   return AVZ_OK;
 }
 
-// hist_bins and n_fft of every state buffer reset in this process, by address: what lets a push
-// be refused on the host, the device header unread.
 namespace {
 struct DelayStreamRecord {
   int hist_bins, n_fft;
+  bool operator==(const DelayStreamRecord& o) const {
+    return hist_bins == o.hist_bins && n_fft == o.n_fft;
+  }
 };
-std::mutex g_delay_stream_mu;
-std::unordered_map<const void*, DelayStreamRecord> g_delay_stream_rec;
+StateRegistry<DelayStreamRecord> g_delay_states;
 }  // namespace
 
 extern "C" long long avz_delay_stream_state_bytes(const avz_plan* p, int streams, int hist_bins) {
@@ -1741,25 +1765,15 @@ extern "C" int avz_delay_stream_reset(const avz_plan* p, void* state, long long 
   rc = delay_stream_state_check(p->cfg, state, state_bytes, streams, hist_bins);
   if (rc != AVZ_OK) return rc;
   if (misaligned(select, 4)) return AVZ_ERR_ALIGN;
-  const DelayStreamRecord now{hist_bins, p->cfg.n_fft};
-  {
-    // a partial reset may not change what the other streams of the buffer were laid out for
-    std::lock_guard<std::mutex> lock(g_delay_stream_mu);
-    auto it = g_delay_stream_rec.find(state);
-    if (select && (it == g_delay_stream_rec.end() || it->second.hist_bins != hist_bins ||
-                   it->second.n_fft != now.n_fft))
-      return AVZ_ERR_ARG;
-    g_delay_stream_rec[state] = now;
-  }
+  if (!g_delay_states.record(state, {hist_bins, p->cfg.n_fft}, select != nullptr))
+    return AVZ_ERR_ARG;
   avz::DelayStreamArgs s{};
   s.streams = streams;
-  s.nb = hist_bins;
+  s.p.nb = hist_bins;
   s.state = static_cast<unsigned char*>(state);
   s.state_stride = avz::DelayStreamLayout(p->cfg.n_fft, hist_bins).stride;
   s.select = select;
-  rc = avz_launch_delay_stream_reset(p->cfg.n_fft, &s, stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_delay_stream_reset(p->cfg.n_fft, &s, stream));
 }
 
 extern "C" int avz_delay_stream_push(const avz_plan* p, const avz_delay_stream_args* a,
@@ -1769,13 +1783,7 @@ extern "C" int avz_delay_stream_push(const avz_plan* p, const avz_delay_stream_a
   if (rc != AVZ_OK) return rc;
   const avz_config& c = p->cfg;
   const int N = c.n_fft;
-  {
-    std::lock_guard<std::mutex> lock(g_delay_stream_mu);
-    auto it = g_delay_stream_rec.find(a->state);
-    if (it == g_delay_stream_rec.end() || it->second.hist_bins != a->hist_bins ||
-        it->second.n_fft != N)
-      return AVZ_ERR_ARG;
-  }
+  if (!g_delay_states.matches(a->state, {a->hist_bins, N})) return AVZ_ERR_ARG;
   avz::DelayStreamArgs k{};
   k.streams = a->streams;
   k.hops = a->hops;
@@ -1786,23 +1794,8 @@ extern "C" int avz_delay_stream_push(const avz_plan* p, const avz_delay_stream_a
   k.mix_stride = a->mix_stride;
   k.ch_stride = a->ch_stride;
   k.angle_deg = a->angle_deg;
-  k.plan_angle = c.angle_deg;
-  k.nb = a->hist_bins;
-  k.smooth = a->smooth;
-  k.max_peaks = a->max_peaks;
-  k.rel_height = a->rel_height;
-  k.min_sep = a->min_sep;
-  // avz_delay_mask's grid
-  k.dmax = c.mic_d * (double)c.fs / c.c_sound;
-  k.R = 1.25 * k.dmax;
-  k.bin_w = 2.0 * k.R / a->hist_bins;
-  const double lo = std::ceil(a->f_lo_hz * N / (double)c.fs);
-  k.k_lo = lo >= N ? N : std::max(1, (int)lo);  // above N / 2: an empty band
-  k.k_hi = -1;  // empty band: no spacing, no delay to find
-  if (k.R > 0.0 && std::isfinite(k.R)) {
-    const double lim = std::ceil(N / (2.0 * k.R)) - 1.0;  // largest k with omega_k R < pi
-    k.k_hi = lim >= N / 2 ? N / 2 : (int)lim;
-  }
+  k.p = delay_params(c, a->hist_bins, a->smooth, a->max_peaks, a->rel_height, a->min_sep,
+                     a->f_lo_hz);
   k.mask = a->mask;
   k.m_sb = a->mask_stride_b;
   k.m_sf = a->mask_stride_f;
@@ -1813,7 +1806,5 @@ extern "C" int avz_delay_stream_push(const avz_plan* p, const avz_delay_stream_a
   k.state = static_cast<unsigned char*>(a->state);
   k.state_stride = avz::DelayStreamLayout(N, a->hist_bins).stride;
   k.xwin = p->xwin;
-  rc = avz_launch_delay_stream_push(N, &k, stream);
-  if (rc == AVZ_ERR_HIP) g_last_hip = hipGetErrorString(hipGetLastError());
-  return rc;
+  return hip_rc(avz_launch_delay_stream_push(N, &k, stream));
 }

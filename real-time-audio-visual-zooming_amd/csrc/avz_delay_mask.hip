@@ -2,7 +2,8 @@
 // (avz_delay_mask; the contract is in include/avz.h and DESIGN.md section 17, the fp64
 // restatement in avz/delay_mask.py).
 //
-// Three launches, no spectrum in memory:
+// Three launches, no spectrum in memory; the arithmetic of each stage (pair, deposit, peaks,
+// rotation, cost) is avz_delay_common.hpp's, this file holds the batch layout around it:
 //   avz_delay_hist_kernel<N>   one block per (utterance, 16 frames), avz_stft_kernel's framing
 //                              and packed two-mic transform. Thread (bin k, frame group) turns
 //                              its bins into (u, w) pairs in place in the LDS slots (only that
@@ -11,8 +12,8 @@
 //                              order and the segments are added in order: the block's partial
 //                              histogram, written to the workspace. No atomics anywhere.
 //   avz_delay_peaks_kernel     one block per utterance: adds the partials in block order
-//                              (fp64), smooths, finds and ranks the peaks, writes the candidate
-//                              list (delta_t first) to the workspace and the optional outputs.
+//                              (fp64), then delay_peaks: the candidate list (delta_t first) to
+//                              the workspace and the optional outputs.
 //   avz_delay_label_kernel<N>  the transform again; thread (bin k, frame group) holds the 1 + J
 //                              rotations of its bin in registers, writes its decisions in place
 //                              into the slots, and the block stores them frame-fastest.
@@ -117,34 +118,22 @@ __global__ void __launch_bounds__(kStftThreads, 1) avz_delay_hist_kernel(DelayAr
   // (u, w) of every band pair, in place: Z_f[kk] <- (u, w)
   BinMap<N> bm;
   bm.init(tid);
-  if (bm.kk >= A.k_lo && bm.kk <= A.k_hi) {
-    // u = arg(X) / (omega_k bin_w) + nb / 2 - 1 / 2
-    const float cu = (float)((double)N / (6.283185307179586476925 * bm.kk * A.bin_w));
-    const float u0 = 0.5f * (float)A.nb - 0.5f;
+  if (bm.kk >= A.p.k_lo && bm.kk <= A.p.k_hi) {
+    const float cu = delay_u_scale(N, bm.kk, A.p.bin_w);
+    const float u0 = 0.5f * (float)A.p.nb - 0.5f;
 #pragma unroll
     for (int q = 0; q < BinMap<N>::FPT; ++q) {
       const int f = bm.fa + q;
       cf* Z = slot_ptr<N>(lds, f);
-      cf y0, y1;
-      split_pair(Z[bm.kk], Z[(N - bm.kk) & (N - 1)], y0, y1);
-      // X = Y1 conj(Y0); w = |X| as |Y0| |Y1| (X^2 would leave fp32's range at low levels)
-      const float xr = fmaf(y1.x, y0.x, y1.y * y0.y);
-      const float xi = fmaf(y1.y, y0.x, -(y1.x * y0.y));
-      float w = sqrtf(fmaf(y0.x, y0.x, y0.y * y0.y)) * sqrtf(fmaf(y1.x, y1.x, y1.y * y1.y));
-      float u = fmaf(atan2f(xi, xr), cu, u0);
-      if (!(fabsf(u) < __builtin_inff()) || !(w < __builtin_inff()) || f0 + f >= T) {
-        u = -4.0f;  // no deposit: a non-finite pair, or a frame past the utterance
-        w = 0.0f;
-      }
-      Z[bm.kk] = {u, w};
+      Z[bm.kk] = delay_pair(Z[bm.kk], Z[(N - bm.kk) & (N - 1)], cu, u0, f0 + f < T);
     }
   }
   __syncthreads();
 
   // owner-computes: thread (bin i, segment s) scans pairs [p0, p1) of the band in order
-  const int nb = A.nb;
+  const int nb = A.p.nb;
   const int S = kStftThreads / nb;
-  const int nband = A.k_hi >= A.k_lo ? A.k_hi - A.k_lo + 1 : 0;
+  const int nband = A.p.k_hi >= A.p.k_lo ? A.p.k_hi - A.p.k_lo + 1 : 0;
   const int P = nband * kDelayFrames;
   double* seg = reinterpret_cast<double*>(lds + G::CARRY_OFF);  // [S][nb] <= 512 f64
   const int i = tid % nb, s = tid / nb;
@@ -153,12 +142,7 @@ __global__ void __launch_bounds__(kStftThreads, 1) avz_delay_hist_kernel(DelayAr
     const float fi = (float)i;
     double acc = 0.0;
     for (int p = p0; p < p1; ++p) {
-      const cf e = slot_ptr<N>(lds, p % kDelayFrames)[A.k_lo + p / kDelayFrames];
-      const float fl = floorf(e.x);
-      const float phi = e.x - fl;
-      const float t = fi - fl;  // 0: this bin is i0, 1: it is i0 + 1
-      const float wt = t == 0.0f ? 1.0f - phi : (t == 1.0f ? phi : 0.0f);
-      acc += (double)(wt * e.y);
+      acc += delay_deposit(slot_ptr<N>(lds, p % kDelayFrames)[A.p.k_lo + p / kDelayFrames], fi);
     }
     seg[s * nb + i] = acc;
   }
@@ -175,7 +159,7 @@ constexpr int kPeakThreads = 256;
 __global__ void __launch_bounds__(kPeakThreads) avz_delay_peaks_kernel(DelayArgs A, int n_fft) {
   __shared__ double hs[2][kDelayMaxBins + 3];
   __shared__ double c_h[kDelayMaxBins + 3], c_d[kDelayMaxBins + 3];
-  const int b = blockIdx.x, tid = threadIdx.x, nb = A.nb;
+  const int b = blockIdx.x, tid = threadIdx.x, nb = A.p.nb;
   const int H = n_fft / 2;
   const int L = min(A.len[b], A.max_len);
   if (L < n_fft) {
@@ -195,62 +179,13 @@ __global__ void __launch_bounds__(kPeakThreads) avz_delay_peaks_kernel(DelayArgs
     if (A.hist_out) A.hist_out[(long long)b * nb + i] = h;
   }
   __syncthreads();
-  int cur = 0;
-  for (int pass = 0; pass < A.smooth; ++pass) {
-    for (int i = tid; i < nb; i += kPeakThreads) {
-      const double l = i > 0 ? hs[cur][i - 1] : 0.0, r = i + 1 < nb ? hs[cur][i + 1] : 0.0;
-      hs[cur ^ 1][i] = 0.25 * l + 0.5 * hs[cur][i] + 0.25 * r;
-    }
-    cur ^= 1;
-    __syncthreads();
-  }
-  const double* h = hs[cur];
-  double top = h[0];  // numpy's max: a NaN stays
-  for (int i = 1; i < nb; ++i) {
-    const double v = h[i];
-    top = (v > top || v != v) ? v : top;
-  }
-  const double theta = A.angle_deg ? A.angle_deg[b] : A.plan_angle;
-  const double d_t = A.dmax * cos(theta * (3.14159265358979323846 / 180.0));
-  for (int i = tid; i < nb; i += kPeakThreads) {
-    const double l = i > 0 ? h[i - 1] : 0.0, r = i + 1 < nb ? h[i + 1] : 0.0, m = h[i];
-    bool cand = top > 0.0 && m > l && m >= r && m >= A.rel_height * top;
-    const double den = l - 2.0 * m + r;
-    const double o = den == 0.0 ? 0.0 : 0.5 * (l - r) / den;
-    const double d = -A.R + ((double)i + 0.5 + o) * A.bin_w;
-    if (cand && fabs(d - d_t) <= A.min_sep * A.dmax) cand = false;  // the target itself
-    c_h[i] = cand ? m : -1.0;  // a candidate's height is > 0
-    c_d[i] = d;
-  }
-  __syncthreads();
-  // rank among the candidates: higher first, ties to the lower bin
-  int total = 0;
-  for (int j = 0; j < nb; ++j) total += c_h[j] >= 0.0 ? 1 : 0;
-  const int J = min(total, A.max_peaks);
-  double* list = A.list + (long long)b * kDelayList;
-  double* dout = A.delays_out ? A.delays_out + (long long)b * kDelayList : nullptr;
-  for (int i = tid; i < nb; i += kPeakThreads) {
-    const double m = c_h[i];
-    if (!(m >= 0.0)) continue;
-    int rank = 0;
-    for (int j = 0; j < nb; ++j) {
-      const double v = c_h[j];
-      rank += (v > m || (v == m && j < i)) ? 1 : 0;
-    }
-    if (rank < J) {
-      list[1 + rank] = c_d[i];
-      if (dout) dout[1 + rank] = c_d[i];
-    }
-  }
+  const double d_t = delay_target(A.p, A.angle_deg ? A.angle_deg[b] : A.p.plan_angle);
+  const int J = delay_peaks<kPeakThreads>(
+      A.p, hs[0], kDelayMaxBins + 3, c_h, c_d, d_t, A.list + (long long)b * kDelayList,
+      A.delays_out ? A.delays_out + (long long)b * kDelayList : nullptr);
   if (tid == 0) {
-    list[0] = d_t;
-    if (dout) dout[0] = d_t;
     A.count[b] = J;
     if (A.n_peaks) A.n_peaks[b] = J;
-  }
-  if (tid > J && tid < kDelayList) {
-    list[tid] = __builtin_nan("");
-    if (dout) dout[tid] = __builtin_nan("");
   }
 }
 
@@ -279,11 +214,7 @@ __global__ void __launch_bounds__(kStftThreads, 1) avz_delay_label_kernel(DelayA
   cf rot[kDelayList];
   static_for<0, kDelayList>([&](auto j) {
     rot[j] = {1.0f, 0.0f};
-    if (j <= J) {  // block-uniform
-      double sn, cs;
-      sincospi(2.0 * (double)bm.kk * list[j] / (double)N, &sn, &cs);
-      rot[j] = {(float)cs, (float)sn};
-    }
+    if (j <= J) rot[j] = delay_rotation(bm.kk, list[j], N);  // block-uniform
   });
   __syncthreads();
 
@@ -293,11 +224,7 @@ __global__ void __launch_bounds__(kStftThreads, 1) avz_delay_label_kernel(DelayA
     cf y0, y1;
     split_pair(Z[bm.kk], Z[(N - bm.kk) & (N - 1)], y0, y1);
     float cost[kDelayList];
-    static_for<0, kDelayList>([&](auto j) {
-      const cf r = c_mul(rot[j], y0);
-      const float dx = y1.x - r.x, dy = y1.y - r.y;
-      cost[j] = fmaf(dx, dx, dy * dy);
-    });
+    static_for<0, kDelayList>([&](auto j) { cost[j] = delay_cost(rot[j], y0, y1); });
     bool other = false;
     static_for<1, kDelayList>([&](auto j) { other = other || (j <= J && cost[j] < cost[0]); });
     Z[bm.kk].x = other ? 0.0f : 1.0f;
@@ -335,7 +262,7 @@ static int launch_delay_t(const DelayArgs* a, hipStream_t st) {
 extern "C" int avz_launch_delay_mask(int n_fft, const DelayArgs* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (a->batch <= 0) return 0;
-  if (a->nb < 1 || a->nb > kDelayMaxBins) return -1;
+  if (a->p.nb < 1 || a->p.nb > kDelayMaxBins) return -1;
   if (n_fft == 1024) return launch_delay_t<1024>(a, st);
   if (n_fft == 512) return launch_delay_t<512>(a, st);
   return -4;

@@ -1,12 +1,11 @@
 // avz_delay_mask.hpp — host/device argument block of the blind delay-histogram mask
 // (avz_delay_mask, avz_delay_mask.hip; not part of the public ABI).
 #pragma once
+#include "avz_delay_common.hpp"
 
 namespace avz {
 
-constexpr int kDelayFrames = 16;      // frames per block of the histogram and label kernels
-constexpr int kDelayMaxBins = 257;    // hist_bins <= this
-constexpr int kDelayList = 8;         // delta_t + at most 7 kept delays
+constexpr int kDelayFrames = 16;  // frames per block of the histogram and label kernels
 
 // Workspace of one call: per-block histogram partials [batch][nblk][hist_bins] f64 (a block's
 // sums over its 16 frames; blocks past an utterance's frames are never written nor read), the
@@ -30,12 +29,8 @@ struct DelayArgs {
   int max_len, max_frames, nblk;
   const float* mix;           // [B][2][..] planar
   long long mix_stride, ch_stride;
-  const double* angle_deg;    // [B] or null = plan_angle
-  double plan_angle;
-  int nb, smooth, max_peaks;
-  double rel_height, min_sep;
-  double dmax, R, bin_w;      // delta_max = d fs / c, R = 1.25 delta_max, bin_w = 2 R / nb (samples)
-  int k_lo, k_hi;             // the histogram's band (k_hi < k_lo: empty)
+  const double* angle_deg;    // [B] or null = p.plan_angle
+  DelayParams p;
   float* mask;                // M[b * m_sb + k * m_sf + t * m_st]
   long long m_sb, m_sf, m_st;
   double* hist_out;           // [B][nb] or null

@@ -6,20 +6,21 @@
 //
 // Layout: one 256-thread block per stream, resident for the whole call; the block walks the
 // call's hops in groups of the eight frames its eight lane groups hold (StreamGeo<N>, as
-// avz_stream_kernel). Per group:
+// avz_stream_kernel). The arithmetic of each stage (pair, deposit, peaks, rotation, cost) is
+// avz_delay_common.hpp's, shared with avz_delay_mask.hip; this file holds the streaming layout
+// around it. Per group:
 //   transform   stream_transform of mic0 + i mic1 into the eight slots;
 //   pairs       thread (bin k, frame) turns its band bins into (u, w) in place in the slot (only
-//               that thread ever reads Z[k] and Z[N - k]): avz_delay_hist_kernel's arithmetic;
+//               that thread ever reads Z[k] and Z[N - k]);
 //   deposits    all frames at once: thread (frame, segment s, histogram bin i) scans its fixed
 //               share of that frame's band pairs in order and adds what falls on bin i (fp64);
 //   recursion   frame by frame, the only serial part: h <- forget h + (the segments added in
-//   and peaks   order), the smoothing passes, the candidate test and the ranking by counting of
-//               avz_delay_peaks_kernel; the frame's list and J go to a table in LDS and to
-//               delays_out / n_peaks;
+//   and peaks   order), then delay_peaks on h_t; the frame's list and J go to a table in LDS and
+//               to delays_out / n_peaks;
 //   transform   again (the pairs overwrote the band's bins);
 //   labels      all frames at once: thread (bin k) holds delta_0's rotation once and forms the
-//               others per frame from the table (fp64 sincospi rounded to fp32), writes its
-//               decisions in place and the block stores them through the caller's strides.
+//               others per frame from the table, writes its decisions in place and the block
+//               stores them through the caller's strides.
 // A frame's arithmetic is the same instruction sequence whatever its slot, group or call and
 // reads nothing of another stream, and every sum has a fixed order that depends on the frame
 // alone: a stream's results do not depend on how its hops are grouped into calls, on its index
@@ -45,9 +46,9 @@ struct DelayStreamGeo {
   static constexpr int CD_OFF = CH_OFF + NBP * 8;
   static constexpr int SEG_OFF = CD_OFF + NBP * 8;
   static constexpr int LIST_OFF = SEG_OFF + SG::NSLOT * NBP * 8;
-  static constexpr int J_OFF = LIST_OFF + SG::NSLOT * kDelayStreamList * 8;
+  static constexpr int J_OFF = LIST_OFF + SG::NSLOT * kDelayList * 8;
   static constexpr int LDS_BYTES = J_OFF + ((SG::NSLOT * 4 + 15) & ~15);
-  static_assert(NBP >= kDelayStreamMaxBins, "a row holds every histogram size");
+  static_assert(NBP >= kDelayMaxBins, "a row holds every histogram size");
   static_assert(H_OFF % 8 == 0, "f64 alignment");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
@@ -62,10 +63,10 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
   using C = KCfg<N>;
   using SG = StreamGeo<N>;
   using DG = DelayStreamGeo<N>;
-  constexpr int H = SG::H, F = SG::F, NSLOT = SG::NSLOT, L8 = kDelayStreamList;
+  constexpr int H = SG::H, F = SG::F, NSLOT = SG::NSLOT, L8 = kDelayList;
   const int s = blockIdx.x;
   if (A.active && A.active[s] == 0) return;
-  const int nb = A.nb;
+  const int nb = A.p.nb;
   const DelayStreamLayout lay(N, nb);
   unsigned char* st = A.state + (long long)s * A.state_stride;
   DelayStreamHeader* hdr = reinterpret_cast<DelayStreamHeader*>(st);
@@ -88,9 +89,9 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
 
   const bool adapt = !A.adapt || A.adapt[s] != 0;
   const double lam = A.forget;
-  double theta = A.angle_deg ? A.angle_deg[s] : A.plan_angle;
-  if (theta != theta) theta = A.plan_angle;  // NaN: the plan's
-  const double d_t = A.dmax * cos(theta * (3.14159265358979323846 / 180.0));
+  double theta = A.angle_deg ? A.angle_deg[s] : A.p.plan_angle;
+  if (theta != theta) theta = A.p.plan_angle;  // NaN: the plan's
+  const double d_t = delay_target(A.p, theta);
 
   C::Fft::fill_twiddles(twid, tid, kStreamThreads);
   for (int n = tid; n < N; n += kStreamThreads) win[n] = A.xwin[n];
@@ -107,7 +108,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
   const float* x0 = A.mix + (long long)s * A.mix_stride;
   const float* x1 = x0 + A.ch_stride;
   float* M = A.mask + (long long)s * A.m_sb;
-  const int nband = A.k_hi >= A.k_lo ? A.k_hi - A.k_lo + 1 : 0;
+  const int nband = A.p.k_hi >= A.p.k_lo ? A.p.k_hi - A.p.k_lo + 1 : 0;
   const int S = delay_stream_segments(nb);
   const int per = S * nb;  // deposit items of one frame: <= 257
 
@@ -122,22 +123,9 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
     {
       const float u0 = 0.5f * (float)nb - 0.5f;
       for (int idx = tid; idx < nf * nband; idx += kStreamThreads) {
-        const int f = idx / nband, k = A.k_lo + idx % nband;
-        // u = arg(X) / (omega_k bin_w) + nb / 2 - 1 / 2
-        const float cu = (float)((double)N / (6.283185307179586476925 * k * A.bin_w));
+        const int f = idx / nband, k = A.p.k_lo + idx % nband;
         cf* Z = slot_ptr<N>(lds, f);
-        cf y0, y1;
-        split_pair(Z[k], Z[(N - k) & (N - 1)], y0, y1);
-        // X = Y1 conj(Y0); w = |X| as |Y0| |Y1| (X^2 would leave fp32's range at low levels)
-        const float xr = fmaf(y1.x, y0.x, y1.y * y0.y);
-        const float xi = fmaf(y1.y, y0.x, -(y1.x * y0.y));
-        float w = sqrtf(fmaf(y0.x, y0.x, y0.y * y0.y)) * sqrtf(fmaf(y1.x, y1.x, y1.y * y1.y));
-        float u = fmaf(atan2f(xi, xr), cu, u0);
-        if (!(fabsf(u) < __builtin_inff()) || !(w < __builtin_inff())) {
-          u = -4.0f;  // no deposit: a non-finite pair
-          w = 0.0f;
-        }
-        Z[k] = {u, w};
+        Z[k] = delay_pair(Z[k], Z[(N - k) & (N - 1)], delay_u_scale(N, k, A.p.bin_w), u0, true);
       }
     }
     __syncthreads();
@@ -147,22 +135,15 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
       const int f = idx / per, r = idx % per;
       const int sg = r / nb, i = r % nb;
       const int p0 = (int)((long long)nband * sg / S), p1 = (int)((long long)nband * (sg + 1) / S);
-      const cf* Zb = slot_ptr<N>(lds, f) + A.k_lo;
+      const cf* Zb = slot_ptr<N>(lds, f) + A.p.k_lo;
       const float fi = (float)i;
       double acc = 0.0;
-      for (int p = p0; p < p1; ++p) {
-        const cf e = Zb[p];
-        const float fl = floorf(e.x);
-        const float phi = e.x - fl;
-        const float t = fi - fl;  // 0: this bin is i0, 1: it is i0 + 1
-        const float wt = t == 0.0f ? 1.0f - phi : (t == 1.0f ? phi : 0.0f);
-        acc += (double)(wt * e.y);
-      }
+      for (int p = p0; p < p1; ++p) acc += delay_deposit(Zb[p], fi);
       seg[idx] = acc;  // [f][sg][i]
     }
     __syncthreads();
 
-    // frame by frame: the recursion, then avz_delay_peaks_kernel's stage 2 on h_t
+    // frame by frame: the recursion, then delay_peaks on h_t
     for (int f = 0; f < nf; ++f) {
       for (int i = tid; i < nb; i += kStreamThreads) {
         double hv = h[i];
@@ -175,63 +156,12 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
         hs0[i] = hv;
       }
       __syncthreads();
-      int cur = 0;
-      for (int pass = 0; pass < A.smooth; ++pass) {
-        const double* a = hs0 + cur * DG::NBP;
-        double* o = hs0 + (cur ^ 1) * DG::NBP;
-        for (int i = tid; i < nb; i += kStreamThreads) {
-          const double l = i > 0 ? a[i - 1] : 0.0, r = i + 1 < nb ? a[i + 1] : 0.0;
-          o[i] = 0.25 * l + 0.5 * a[i] + 0.25 * r;
-        }
-        cur ^= 1;
-        __syncthreads();
-      }
-      const double* hh = hs0 + cur * DG::NBP;
-      double top = hh[0];  // numpy's max: a NaN stays
-      for (int i = 1; i < nb; ++i) {
-        const double v = hh[i];
-        top = (v > top || v != v) ? v : top;
-      }
-      for (int i = tid; i < nb; i += kStreamThreads) {
-        const double l = i > 0 ? hh[i - 1] : 0.0, r = i + 1 < nb ? hh[i + 1] : 0.0, m = hh[i];
-        bool cand = top > 0.0 && m > l && m >= r && m >= A.rel_height * top;
-        const double den = l - 2.0 * m + r;
-        const double o = den == 0.0 ? 0.0 : 0.5 * (l - r) / den;
-        const double d = -A.R + ((double)i + 0.5 + o) * A.bin_w;
-        if (cand && fabs(d - d_t) <= A.min_sep * A.dmax) cand = false;  // the target itself
-        c_h[i] = cand ? m : -1.0;  // a candidate's height is > 0
-        c_d[i] = d;
-      }
-      __syncthreads();
-      // rank among the candidates: higher first, ties to the lower bin
-      int total = 0;
-      for (int j = 0; j < nb; ++j) total += c_h[j] >= 0.0 ? 1 : 0;
-      const int J = min(total, A.max_peaks);
-      double* list = tab + f * L8;
       const long long row = (long long)s * A.hops + (j0 + f);
-      double* dout = A.delays_out ? A.delays_out + row * L8 : nullptr;
-      for (int i = tid; i < nb; i += kStreamThreads) {
-        const double m = c_h[i];
-        if (!(m >= 0.0)) continue;
-        int rank = 0;
-        for (int j = 0; j < nb; ++j) {
-          const double v = c_h[j];
-          rank += (v > m || (v == m && j < i)) ? 1 : 0;
-        }
-        if (rank < J) {
-          list[1 + rank] = c_d[i];
-          if (dout) dout[1 + rank] = c_d[i];
-        }
-      }
+      const int J = delay_peaks<kStreamThreads>(A.p, hs0, DG::NBP, c_h, c_d, d_t, tab + f * L8,
+                                                A.delays_out ? A.delays_out + row * L8 : nullptr);
       if (tid == 0) {
-        list[0] = d_t;
-        if (dout) dout[0] = d_t;
         Jt[f] = J;
         if (A.n_peaks) A.n_peaks[row] = J;
-      }
-      if (tid > J && tid < L8) {
-        list[tid] = __builtin_nan("");
-        if (dout) dout[tid] = __builtin_nan("");
       }
       __syncthreads();  // the list is complete; hs, c_h and c_d are free for the next frame
     }
@@ -244,28 +174,17 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
     for (int k = tid; k < N / 2; k += kStreamThreads) {
       const bool dc = k == 0;
       const int kk = dc ? N / 2 : k;
-      cf rot0;
-      {
-        double sn, cs;
-        sincospi(2.0 * (double)kk * d_t / (double)N, &sn, &cs);
-        rot0 = {(float)cs, (float)sn};
-      }
+      const cf rot0 = delay_rotation(kk, d_t, N);
       for (int f = 0; f < nf; ++f) {
         cf* Z = slot_ptr<N>(lds, f);
         cf y0, y1;
         split_pair(Z[kk], Z[(N - kk) & (N - 1)], y0, y1);
-        const cf r0 = c_mul(rot0, y0);
-        const float dx0 = y1.x - r0.x, dy0 = y1.y - r0.y;
-        const float cost0 = fmaf(dx0, dx0, dy0 * dy0);
+        const float cost0 = delay_cost(rot0, y0, y1);
         const int J = Jt[f];
         bool other = false;
         for (int j = 1; j <= J; ++j) {
-          double sn, cs;
-          sincospi(2.0 * (double)kk * tab[f * L8 + j] / (double)N, &sn, &cs);
-          const cf rj = {(float)cs, (float)sn};
-          const cf r = c_mul(rj, y0);
-          const float dx = y1.x - r.x, dy = y1.y - r.y;
-          other = other || fmaf(dx, dx, dy * dy) < cost0;
+          const float cost = delay_cost(delay_rotation(kk, tab[f * L8 + j], N), y0, y1);
+          other = other || cost < cost0;
         }
         Z[kk].x = other ? 0.0f : 1.0f;
         if (dc) Z[0].x = 1.0f;
@@ -312,7 +231,7 @@ __global__ void __launch_bounds__(kStreamThreads) avz_delay_stream_reset_kernel(
   if (threadIdx.x == 0) {
     DelayStreamHeader* hdr = reinterpret_cast<DelayStreamHeader*>(st);
     hdr->count = 0ull;
-    hdr->nb = A.nb;
+    hdr->nb = A.p.nb;
     hdr->n_fft = n_fft;
   }
 }
@@ -334,7 +253,7 @@ static int launch_delay_stream_t(const DelayStreamArgs* a, hipStream_t st) {
 
 extern "C" int avz_launch_delay_stream_push(int n_fft, const DelayStreamArgs* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (a->nb < 1 || a->nb > kDelayStreamMaxBins) return -1;
+  if (a->p.nb < 1 || a->p.nb > kDelayMaxBins) return -1;
   if (n_fft == 1024) return launch_delay_stream_t<1024>(a, st);
   if (n_fft == 512) return launch_delay_stream_t<512>(a, st);
   return -4;

@@ -2,11 +2,9 @@
 // delay-histogram mask (avz_delay_stream_push / _reset, avz_delay_stream.hip; not part of the
 // public ABI).
 #pragma once
+#include "avz_delay_common.hpp"
 
 namespace avz {
-
-constexpr int kDelayStreamMaxBins = 257;  // hist_bins <= this (avz_delay_mask's range)
-constexpr int kDelayStreamList = 8;       // delta_t + at most 7 kept delays
 
 struct DelayStreamHeader {
   unsigned long long count;  // frames pushed since the reset
@@ -33,12 +31,8 @@ struct DelayStreamArgs {
   const int* adapt;           // [streams] or null: 0 = the histogram freezes
   const float* mix;           // [streams][2][hops * H] planar
   long long mix_stride, ch_stride;
-  const double* angle_deg;    // [streams] or null; a NaN entry = plan_angle
-  double plan_angle;
-  int nb, smooth, max_peaks;
-  double rel_height, min_sep;
-  double dmax, R, bin_w;      // avz_delay_mask's grid (samples)
-  int k_lo, k_hi;             // the histogram's band (k_hi < k_lo: empty)
+  const double* angle_deg;    // [streams] or null; a NaN entry = p.plan_angle
+  DelayParams p;
   float* mask;                // M[s * m_sb + k * m_sf + j * m_st], j = hop of this call
   long long m_sb, m_sf, m_st;
   double* hist_out;           // [streams][nb] or null

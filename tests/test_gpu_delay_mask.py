@@ -39,7 +39,7 @@ def _plan(n_fft, d, max_samples=None, max_batch=3, **kw):
 
 
 def run(dev, n_fft, d, order=(0, 1, 2), angles=None, scale=1.0, nan_rows=(), lens=None,
-        hist_bins=65):
+        hist_bins=65, smooth=3, max_peaks=3, rel_height=0.25):
     """One avz_delay_mask call through the C ABI on sentinel-filled, padded buffers:
     dict(mask [B, F + 2, T + 3] (NaN-filled), hist [B, nb], delays [B, 8], n [B], lens, T)."""
     import torch
@@ -62,7 +62,8 @@ def run(dev, n_fft, d, order=(0, 1, 2), angles=None, scale=1.0, nan_rows=(), len
     ws = torch.full((need,), 0xA5, dtype=torch.uint8, device=dev)  # the library must not rely on zeros
     a = _lib.AvzDelayMaskArgs(batch=B, len=tl.data_ptr(), max_len=max_len, mix=mix.data_ptr(),
                               mix_stride=buf.shape[1], ch_stride=ch, hist_bins=hist_bins,
-                              smooth=3, max_peaks=3, rel_height=0.25, min_sep=0.2, f_lo_hz=100.0,
+                              smooth=smooth, max_peaks=max_peaks, rel_height=rel_height,
+                              min_sep=0.2, f_lo_hz=100.0,
                               mask=mask.data_ptr(), mask_stride_b=mask.stride(0),
                               mask_stride_f=mask.stride(1), mask_stride_t=mask.stride(2),
                               hist_out=hist.data_ptr(), delays_out=delays.data_ptr(),
@@ -216,6 +217,35 @@ def test_other_histogram_sizes_and_the_python_wrapper(gpu_device):
         Tb = frames_of(ln[r], n_fft)
         assert same_bits(M[r, :, :Tb].cpu().numpy(), base["mask"][r][:base["F"], :Tb])
         assert (M[r, :, Tb:] == 0).all()     # a new mask starts as zeros
+
+
+def test_peak_rule_extremes(gpu_device):
+    """The peak stage off its defaults, rel_height 0.01: (smooth, max_peaks) = (0, 0) (no pass,
+    nothing kept: J = 0 and M = 1), (0, 7) (no pass, the cap binds and the list is full: no NaN
+    fill) and (8, 7) (eight passes). N = 512, d = 0.08, utterances 0 and 2 (18 and 11 frames);
+    the fp64 restatement alone finds at least 10 candidates in utterance 0 at (0, 7). Stage 2 of
+    the restatement on the kernel's own hist_out: the same J, delays within 1e-9, NaN beyond J."""
+    n_fft, d, rh = 512, 0.08, 0.01
+    g = DM.delay_grid(n_fft, DC.FS, d, DC.C_SOUND, 65)
+    for smooth, max_peaks in ((0, 0), (0, 7), (8, 7)):
+        got = run(gpu_device, n_fft, d, order=(0, 2), smooth=smooth, max_peaks=max_peaks,
+                  rel_height=rh)
+        Js = []
+        for r in range(2):
+            J, gd = int(got["n"][r]), got["delays"][r]
+            d2, J2, _ = DM.delay_peaks(got["hist"][r], g, 90.0, smooth=smooth, rel_height=rh,
+                                       max_peaks=max_peaks)
+            e_own = np.abs(gd[:1 + J2] - d2[:1 + J2]).max()
+            print(f"smooth {smooth} max_peaks {max_peaks} [{r}]: J {J} (stage 2 on hist_out {J2}), "
+                  f"delays {e_own:.1e} from it")
+            assert J == J2 and np.isnan(gd[1 + J:]).all()
+            assert e_own <= 1e-9
+            Js.append(J)
+            if max_peaks == 0:
+                Tb = frames_of(got["lens"][r], n_fft)
+                assert J == 0 and (got["mask"][r][:got["F"], :Tb] == 1.0).all()
+        if (smooth, max_peaks) == (0, 7):
+            assert 7 in Js  # the cap binds
 
 
 def test_end_to_end_blind_enhancement(gpu_device):

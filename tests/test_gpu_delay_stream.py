@@ -56,7 +56,7 @@ class Run:
 
     def __init__(self, dev, n_fft, d, groups, forget=1.0, order=(0, 1, 2), scale=1.0,
                  nan_rows=(), active=None, adapt=None, angles=None, hist_bins=65, push_bins=None,
-                 x=None, reset_after=None):
+                 x=None, reset_after=None, smooth=3, max_peaks=3, rel_height=0.25):
         import torch
         lib = _lib.lib
         plan = _plan(n_fft, d)
@@ -88,7 +88,8 @@ class Run:
             a = _lib.AvzDelayStreamArgs(
                 streams=B, hops=g, forget=forget, mix=mix.data_ptr() + 4 * j0 * H,
                 mix_stride=buf.shape[1], ch_stride=ch, hist_bins=push_bins or hist_bins,
-                smooth=3, max_peaks=3, rel_height=0.25, min_sep=0.2, f_lo_hz=100.0,
+                smooth=smooth, max_peaks=max_peaks, rel_height=rel_height, min_sep=0.2,
+                f_lo_hz=100.0,
                 mask=mask.data_ptr() + 4 * j0, mask_stride_b=mask.stride(0),
                 mask_stride_f=mask.stride(1), mask_stride_t=1, hist_out=hh.data_ptr(),
                 delays_out=dl.data_ptr(), n_peaks=nn.data_ptr(), state=state.data_ptr(),
@@ -338,6 +339,40 @@ def test_zero_frames_and_other_histogram_sizes(gpu_device, n_fft, d, nb):
     assert not z.hists[-1][1].any() and np.isnan(z.delays[1][:, 1:]).all()
     assert (z.mask[2][:z.F, :4] == 1.0).all() and (z.n[2, :4] == 0).all()
     assert (z.n[2, 5:] > 0).any() and (z.mask[2][:z.F, 5:T] == 0.0).any()
+
+
+def test_peak_rule_extremes(gpu_device):
+    """The peak stage off its defaults, rel_height 0.01: (smooth, max_peaks) = (0, 0) (no pass,
+    nothing kept: J = 0 and M = 1), (0, 7) (no pass, the cap binds and the list is full: no NaN
+    fill) and (8, 7) (eight passes). N = 512, d = 0.08, forget 0.9, streams 0 and 1, their first
+    9 hops pushed as 8 + 1: a full group of frames and a one-frame group; the fp64 restatement
+    alone keeps 7 peaks on most of these frames at (0, 7). h_t is hist_out of the same hops pushed
+    one by one; stage 2 of the restatement on it: the same J, delays within 1e-9, NaN beyond J."""
+    dev, n_fft, d, rh, hops = gpu_device, 512, 0.08, 0.01, 9
+    x = SC.inputs(n_fft, d)[:, :, :hops * (n_fft // 2)]
+    g = DM.delay_grid(n_fft, SC.FS, d, SC.C_SOUND, 65)
+    for smooth, max_peaks in ((0, 0), (0, 7), (8, 7)):
+        kw = dict(order=(0, 1), x=x, smooth=smooth, max_peaks=max_peaks, rel_height=rh)
+        one = Run(dev, n_fft, d, [1] * hops, 0.9, **kw).ok()
+        run = Run(dev, n_fft, d, [8, 1], 0.9, **kw).ok()
+        for c, t in enumerate(run.ends):
+            assert run.hists[c].tobytes() == one.hists[t].tobytes(), t
+        worst = 0.0
+        for s in range(2):
+            assert run.bits(s) == one.bits(s)
+            for t in range(hops):
+                J, gd = int(run.n[s, t]), run.delays[s, t]
+                d2, J2, _ = DM.delay_peaks(one.hists[t][s], g, 90.0, smooth=smooth, rel_height=rh,
+                                           max_peaks=max_peaks)
+                assert J == J2 and np.isnan(gd[1 + J:]).all(), (s, t, J, J2)
+                worst = max(worst, np.abs(gd[:1 + J] - d2[:1 + J]).max())
+        print(f"smooth {smooth} max_peaks {max_peaks}: J {run.n.tolist()}, delays {worst:.1e} "
+              f"from stage 2 on h_t")
+        assert worst <= 1e-9
+        if max_peaks == 0:
+            assert (run.n == 0).all() and (run.mask[:, :run.F, :hops] == 1.0).all()
+        if (smooth, max_peaks) == (0, 7):
+            assert (run.n == 7).any()  # the cap binds
 
 
 def test_mask_columns_align_with_the_beamformer(gpu_device):
