@@ -139,17 +139,18 @@ def dereverb_batch(mix, lengths=None, taps=10, delay=3, iterations=3, n_fft=N_FF
     trimmed to S; samples at or beyond lengths[b] are zero. ``plan``: an un-normalised
     MVDRPlan of this n_fft with max_batch >= 2 B (made here when None)."""
     import torch
+    from . import _args as A
     from .engine import n_frames, wpe_spectral
-    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or not mix.is_cuda:
-        raise ValueError("mix must be float32 [B, 2, S] on the device")
-    B, _, S = mix.shape
+    B, S, _ = A.mic_pair("mix", mix)
     if plan is None:
         plan = _plan(n_fft, B, S)
     hop = plan.hop
+    # wpe_spectral checks status too, but only after plan.stft has launched
+    A.outputs((("status", status, A.ge(B * plan.F), torch.int32),), mix.device)
     if lengths is None:
         frames, max_len = None, S
     else:
-        max_len = int(lengths.max().item())
+        lengths, max_len = A.lengths(lengths, None, B, S, mix.device)
         frames = (torch.div(lengths + (hop - 1), hop, rounding_mode="floor") + 1).to(torch.int32)
     Y = plan.stft(mix, lengths, max_len, stream=stream)
     T = n_frames(max_len, hop)
@@ -328,7 +329,10 @@ def wpe_stream_numpy(x, n_fft=N_FFT, taps=10, delay=3, forget=0.99, power_floor=
     return np.concatenate(outs, axis=1), st
 
 
-class StreamingWPE:
+from .stream import StreamOwner  # noqa: E402  (numpy only at import, like this module)
+
+
+class StreamingWPE(StreamOwner):
     """`streams` independent online-WPE dereverberators over one device state buffer. The
     plan supplies n_fft, the window and max_batch (streams <= plan.cfg.max_batch); its mask
     and beamformer settings play no part. push() returns [streams, 2, hops * hop], one hop
@@ -339,26 +343,15 @@ class StreamingWPE:
                  power_floor=None, q_init: float = 1.0, device=None):
         import torch
         from . import engine
-        self.plan, self.streams = plan, int(streams)
         self.taps, self.delay, self.forget = int(taps), int(delay), float(forget)
         self.power_floor = float(default_power_floor(plan.cfg.n_fft) if power_floor is None
                                  else power_floor)
         self.q_init = float(q_init)
-        self.device = torch.device(device if device is not None else "cuda")
-        nbytes = engine.wpe_stream_state_bytes(plan, self.streams, self.taps, self.delay)
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        super().__init__(plan, streams, device, engine.wpe_stream_state_bytes, self.taps,
+                         self.delay)
         self.G = torch.zeros((self.streams, plan.F, 2 * self.taps, 2), dtype=torch.complex128,
                              device=self.device)
         self.reset()
-
-    def _flags(self, v, name):
-        import torch
-        if v is None:
-            return None
-        t = torch.as_tensor(v, device=self.device).to(torch.int32).contiguous()
-        if tuple(t.shape) != (self.streams,):
-            raise ValueError(f"{name} must have one entry per stream")
-        return t
 
     def reset(self, select=None, stream=None):
         """Start the selected streams (flags per stream; None = all) afresh."""
@@ -372,8 +365,7 @@ class StreamingWPE:
         the dereverberator, one hop behind the input."""
         import torch
         from . import engine
-        if mix.dim() != 3 or mix.shape[0] != self.streams:
-            raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
+        self._block(mix)
         if out is None:
             out = torch.empty(tuple(mix.shape), dtype=torch.float32, device=mix.device)
         return engine.wpe_stream_push(self.plan, self.state, mix, out, taps=self.taps,
@@ -385,10 +377,7 @@ class StreamingWPE:
 
     def flush(self, **kw):
         """Push one hop of zeros: returns the last hop."""
-        import torch
-        z = torch.zeros((self.streams, 2, self.plan.hop), dtype=torch.float32,
-                        device=self.device)
-        return self.push(z, **kw)
+        return self.push(self._zero_hop(), **kw)
 
 
 def apply_wpe_stream(y_mix, taps=10, delay=3, forget=0.99, power_floor=None, q_init=1.0,

@@ -5,6 +5,9 @@
 rt_av_zoom/core/full_audio_generating_pipeline/inference.py:88-118): one call runs
 STFT -> mask -> masked covariance -> MVDR -> apply/post-filter -> iSTFT (-> peak
 normalisation) for a whole batch of utterances in one chain of kernel launches (analysis, solve, synthesis, finalize).
+
+Every tensor argument is checked by avz/_args.py before its address goes to the library:
+dtype, shape, strides, and that it lives on the device of the call's first tensor.
 """
 from __future__ import annotations
 
@@ -13,8 +16,13 @@ from dataclasses import dataclass, field
 
 import torch
 
+from . import _args as A
 from . import _lib
+from ._args import ANY, FULL, ge, ptr, tensor
 from ._lib import AvzBatchArgs, AvzConfig, AvzStreamArgs, check, lib
+
+F32, F64, I32, U8 = torch.float32, torch.float64, torch.int32, torch.uint8
+C64, C128 = torch.complex64, torch.complex128
 
 MASKS = {"ibm": _lib.MASK_IBM, "ipd": _lib.MASK_IPD, "external": _lib.MASK_EXTERNAL,
          "ones": _lib.MASK_ONES}
@@ -63,13 +71,7 @@ class PlanConfig:
     extra: dict = field(default_factory=dict)
 
 
-def _ptr(t):
-    return None if t is None else ct.c_void_p(t.data_ptr())
-
-
-def _stream_handle(stream):
-    s = stream if stream is not None else torch.cuda.current_stream()
-    return ct.c_void_p(s.cuda_stream)
+_stream_handle = A.stream_handle   # the name other code imports
 
 
 class MVDRPlan:
@@ -124,7 +126,7 @@ class MVDRPlan:
         2 elements; None = off)."""
         if counts is not None:
             assert counts.dtype == torch.int64 and counts.is_cuda and counts.numel() >= 2
-        check(lib.avz_plan_set_ibm_stats(self._h, _ptr(counts)), "avz_plan_set_ibm_stats")
+        check(lib.avz_plan_set_ibm_stats(self._h, ptr(counts)), "avz_plan_set_ibm_stats")
         self._ibm_stats = counts  # keep the buffer alive
 
     def set_diagnostics(self, synth_variant: int = 2, ipf_mode: int = 0) -> None:
@@ -169,75 +171,55 @@ class MVDRPlan:
     def _batch_args(self, mix, lengths, max_len, ref_tgt, ref_int, ext_mask, out, peak,
                     cov_out, w_out, workspace, need_out=True):
         """Validated avz_batch_args of a time-domain call (shared by run and the stages)."""
-        if not mix.is_cuda:
-            raise ValueError("mix must be a device tensor")
-        if mix.dtype != torch.float32 or mix.dim() != 3 or mix.shape[1] != 2:
-            raise ValueError("mix must be float32 [B, 2, S]")
-        if mix.stride(2) != 1:
-            raise ValueError("mix must be contiguous along samples")
-        B, _, S = mix.shape
-        dev = mix.device
-        if lengths is None:
-            lengths = torch.full((B,), S, dtype=torch.int32, device=dev)
-            max_len = S
-        if lengths.dtype != torch.int32 or not lengths.is_cuda or lengths.dim() != 1 \
-                or lengths.shape[0] < B:
-            raise ValueError("lengths must be an int32 device tensor of >= B entries")
-        if max_len is None:
-            max_len = int(lengths[:B].max().item())
+        B, S, dev = A.mic_pair("mix", mix)
+        lengths, max_len = A.lengths(lengths, max_len, B, S, dev)
         if max_len > S:
             raise ValueError(f"max_len {max_len} exceeds the {S} samples of mix")
-        T = self.frames(max_len)
         a = AvzBatchArgs()
+        rows = ge(B)
         if need_out:
             if out is None:
                 out = self.alloc_out(B, max_len, dev)
+            else:
+                # at least out_len(max_len) samples a row
+                tensor("out", out, F32, (rows, ge(-(-max_len // self.hop) * self.hop)), dev)
             if peak is None:
                 peak = torch.empty((B,), dtype=torch.float32, device=dev)
-            if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B or \
-                    out.shape[1] < self.out_len(max_len) or out.stride(1) != 1:
-                raise ValueError("out must be float32 [>= B, >= out_len(max_len)]")
-            if peak.dtype != torch.float32 or peak.numel() < B or not peak.is_contiguous():
-                raise ValueError("peak must be a contiguous float32 tensor of >= B entries")
+            else:
+                tensor("peak", peak, F32, rows, dev, FULL)
             a.out = out.data_ptr()
             a.out_stride = out.stride(0)
             a.peak = peak.data_ptr()
         a.batch = B
         a.len = lengths.data_ptr()
-        a.max_len = int(max_len)
+        a.max_len = max_len
         a.mix = mix.data_ptr()
         a.mix_stride = mix.stride(0)
         a.ch_stride = mix.stride(1)
-        for r in (ref_tgt, ref_int):
-            if r is not None and (r.dtype != torch.float32 or r.stride(-1) != 1 or not r.is_cuda
-                                  or r.dim() != 2 or r.shape[0] < B or r.shape[1] < max_len):
-                raise ValueError("references must be float32 device tensors [B, >= max_len]")
+        ref = None if ref_tgt is None and ref_int is None else (rows, ge(max_len))
         if ref_tgt is not None:
+            tensor("ref_tgt", ref_tgt, F32, ref, dev)
             a.ref_tgt = ref_tgt.data_ptr()
             a.ref_stride = ref_tgt.stride(0)
         if ref_int is not None:
+            tensor("ref_int", ref_int, F32, ref, dev)
             a.ref_int = ref_int.data_ptr()
             if ref_tgt is not None and ref_int.stride(0) != ref_tgt.stride(0):
                 raise ValueError("ref_tgt and ref_int must share a stride")
         if ext_mask is not None:
-            if ext_mask.dtype != torch.float32 or not ext_mask.is_cuda or ext_mask.dim() != 3:
-                raise ValueError("ext_mask must be float32 [B, F, T] on the device")
-            if ext_mask.shape[0] < B or ext_mask.shape[1] < self.F or ext_mask.shape[2] < T:
-                raise ValueError(f"ext_mask {tuple(ext_mask.shape)} does not cover "
-                                 f"[B={B}, F={self.F}, T={T}]")
+            tensor("ext_mask", ext_mask, F32, (rows, ge(self.F), ge(self.frames(max_len))), dev,
+                   ANY)
             a.ext_mask = ext_mask.data_ptr()
             a.mask_stride_b, a.mask_stride_f, a.mask_stride_t = ext_mask.stride()
             a.mask_bins, a.mask_frames = ext_mask.shape[1], ext_mask.shape[2]
-        for name, t, last in (("cov_out", cov_out, 5), ("w_out", w_out, 4)):
-            if t is not None and (not t.is_cuda or not t.is_contiguous() or t.numel() < B * self.F * last
-                                  or t.dtype != (torch.float64 if last == 5 else torch.float32)):
-                raise ValueError(f"{name} must be a contiguous device tensor of "
-                                 f"[B, F, {last}] {'float64' if last == 5 else 'float32'}")
-        a.cov_out = 0 if cov_out is None else cov_out.data_ptr()
-        a.w_out = 0 if w_out is None else w_out.data_ptr()
+        if cov_out is not None:
+            tensor("cov_out", cov_out, F64, ge(B * self.F * 5), dev, FULL)
+            a.cov_out = cov_out.data_ptr()
+        if w_out is not None:
+            tensor("w_out", w_out, F32, ge(B * self.F * 4), dev, FULL)
+            a.w_out = w_out.data_ptr()
         if workspace is not None:
-            if workspace.dtype != torch.uint8 or not workspace.is_cuda:
-                raise ValueError("workspace must be a uint8 device tensor")
+            tensor("workspace", workspace, U8, ge(0), dev, ANY)
             a.workspace = workspace.data_ptr()
             a.workspace_bytes = workspace.numel()
         return a, out, peak
@@ -252,7 +234,7 @@ class MVDRPlan:
         Returns (out [B, >= out_len], peak [B])."""
         a, out, peak = self._batch_args(mix, lengths, max_len, ref_tgt, ref_int, ext_mask, out,
                                         peak, cov_out, w_out, workspace)
-        check(lib.avz_mvdr_batch(self._h, ct.byref(a), _stream_handle(stream)), "avz_mvdr_batch")
+        A.call("avz_mvdr_batch", self._h, ct.byref(a), stream=stream)
         return out, peak
 
     # ------------------------------------------------------------------ stage exports
@@ -263,10 +245,10 @@ class MVDRPlan:
         B = mix.shape[0]
         if cov_out is None:
             cov_out = torch.empty((B, self.F, 5), dtype=torch.float64, device=mix.device)
+        # no out, no peak: the sums are this call's only output
         a, _, _ = self._batch_args(mix, lengths, max_len, ref_tgt, ref_int, ext_mask, None, None,
                                    cov_out, None, workspace, need_out=False)
-        check(lib.avz_mvdr_covariance(self._h, ct.byref(a), _stream_handle(stream)),
-              "avz_mvdr_covariance")
+        A.call("avz_mvdr_covariance", self._h, ct.byref(a), stream=stream)
         return cov_out
 
     def solve_covariance(self, cov: torch.Tensor, *, steer=None, w=None, fallback=None,
@@ -274,128 +256,99 @@ class MVDRPlan:
         """Covariance sums [B, F, 5] float64 -> weights [B, F, 4] float32 (Re w0, Im w0,
         Re w1, Im w1) with the plan's beamformer (avz_solve_covariance; oracle_debug.py:66-79).
         steer: optional [F, 2] complex128 device tensor; fallback: optional [B] int32."""
-        if cov.dtype != torch.float64 or cov.dim() != 3 or cov.shape[1:] != (self.F, 5) \
-                or not cov.is_contiguous() or not cov.is_cuda:
-            raise ValueError("cov must be a contiguous float64 [B, F, 5] device tensor")
-        B = cov.shape[0]
+        tensor("cov", cov, F64, (None, self.F, 5), "cuda", FULL)
+        B, dev = cov.shape[0], cov.device
         if w is None:
-            w = torch.empty((B, self.F, 4), dtype=torch.float32, device=cov.device)
-        st = self._steer_ptr(steer)
-        fb = self._fallback_ptr(fallback, B)
-        check(lib.avz_solve_covariance(self._h, B, ct.c_void_p(cov.data_ptr()),
-                                       ct.c_void_p(w.data_ptr()), st, fb, _stream_handle(stream)),
-              "avz_solve_covariance")
+            w = torch.empty((B, self.F, 4), dtype=torch.float32, device=dev)
+        else:
+            tensor("w", w, F32, ge(B * self.F * 4), dev, ANY)
+        A.call("avz_solve_covariance", self._h, B, ptr(cov), ptr(w), self._steer_ptr(steer, dev),
+               self._fallback_ptr(fallback, B, dev), stream=stream)
         return w
 
     def apply_istft(self, mix, w: torch.Tensor, lengths=None, *, max_len=None, gain=None,
                     out=None, peak=None, workspace=None, stream=None):
         """STFT of mix -> S = w^H y (x gain [B, F, T] when given) -> iSTFT/OLA
         (avz_apply_istft; oracle_debug.py:80-94). Returns (out, peak)."""
-        if w.dtype != torch.float32 or not w.is_contiguous() or not w.is_cuda \
-                or w.numel() < mix.shape[0] * self.F * 4:
-            raise ValueError("w must be a contiguous float32 [B, F, 4] device tensor")
         a, out, peak = self._batch_args(mix, lengths, max_len, None, None, gain, out, peak, None,
                                         None, workspace)
-        check(lib.avz_apply_istft(self._h, ct.byref(a), ct.c_void_p(w.data_ptr()),
-                                  _stream_handle(stream)), "avz_apply_istft")
+        tensor("w", w, F32, ge(a.batch * self.F * 4), mix.device, FULL)
+        A.call("avz_apply_istft", self._h, ct.byref(a), ptr(w), stream=stream)
         return out, peak
 
     # ------------------------------------------------------------------ spectral domain
-    def _steer_ptr(self, steer):
-        if steer is None:
-            return None
-        if steer.dtype != torch.complex128 or steer.shape != (self.F, 2) or not steer.is_cuda \
-                or not steer.is_contiguous():
-            raise ValueError("steer must be a contiguous complex128 [F, 2] device tensor")
-        return ct.c_void_p(steer.data_ptr())
+    def _steer_ptr(self, steer, dev):
+        if steer is not None:
+            tensor("steer", steer, C128, (self.F, 2), dev, FULL)
+        return ptr(steer)
 
-    def _fallback_ptr(self, fallback, B):
-        if fallback is None:
-            return None
-        if fallback.dtype != torch.int32 or fallback.numel() < B or not fallback.is_cuda:
-            raise ValueError("fallback must be an int32 device tensor of >= B entries")
-        return ct.c_void_p(fallback.data_ptr())
+    def _fallback_ptr(self, fallback, B, dev):
+        if fallback is not None:
+            tensor("fallback", fallback, I32, ge(B), dev, ANY)
+        return ptr(fallback)
 
     def beamform_spectral(self, Y: torch.Tensor, mask: torch.Tensor, *, steer=None, S=None,
                           cov_out=None, w_out=None, fallback=None, stream=None) -> torch.Tensor:
         """Y [B, 2, F, T] complex64, mask [B, F, T] float32 target probability -> S [B, F, T]
         complex64 (avz_beamform_spectral: batch_mvdr or hybrid_hard_null_bf per the plan's
         beamformer, the plan's post-filter fused)."""
-        if Y.dtype != torch.complex64 or Y.dim() != 4 or Y.shape[1] != 2 or Y.shape[2] != self.F \
-                or Y.stride(3) != 1 or not Y.is_cuda:
-            raise ValueError(f"Y must be complex64 [B, 2, {self.F}, T] (t contiguous) on the device")
+        tensor("Y", Y, C64, (None, 2, self.F, None), "cuda")
         B, _, _, T = Y.shape
-        if mask.dtype != torch.float32 or mask.dim() != 3 or tuple(mask.shape) != (B, self.F, T) \
-                or mask.stride(2) != 1 or not mask.is_cuda:
-            raise ValueError(f"mask must be float32 [{B}, {self.F}, {T}] (t contiguous)")
+        dev = Y.device
+        tensor("mask", mask, F32, (B, self.F, T), dev)
         if S is None:
-            S = torch.empty((B, self.F, T), dtype=torch.complex64, device=Y.device)
-        if S.dtype != torch.complex64 or tuple(S.shape) != (B, self.F, T) or S.stride(2) != 1:
-            raise ValueError("S must be complex64 [B, F, T] (t contiguous)")
-        for name, t, last, dt in (("cov_out", cov_out, 5, torch.float64),
-                                  ("w_out", w_out, 4, torch.float32)):
-            if t is not None and (t.dtype != dt or not t.is_contiguous() or not t.is_cuda
-                                  or t.numel() < B * self.F * last):
-                raise ValueError(f"{name} must be a contiguous [B, F, {last}] {dt} device tensor")
+            S = torch.empty((B, self.F, T), dtype=torch.complex64, device=dev)
+        else:
+            tensor("S", S, C64, (B, self.F, T), dev)
+        A.outputs((("cov_out", cov_out, ge(B * self.F * 5), F64),
+                   ("w_out", w_out, ge(B * self.F * 4), F32)), dev)
         a = _lib.AvzSpectralArgs()
         a.batch, a.frames = B, T
-        a.Y = Y.data_ptr()
+        a.Y = ptr(Y)
         a.y_stride_b, a.y_stride_m, a.y_stride_f = Y.stride(0), Y.stride(1), Y.stride(2)
-        a.mask = mask.data_ptr()
+        a.mask = ptr(mask)
         a.mask_stride_b, a.mask_stride_f = mask.stride(0), mask.stride(1)
-        st = self._steer_ptr(steer)
-        a.steer = st.value if st is not None else None
-        a.S = S.data_ptr()
+        a.steer = self._steer_ptr(steer, dev)
+        a.S = ptr(S)
         a.s_stride_b, a.s_stride_f = S.stride(0), S.stride(1)
-        a.cov_out = None if cov_out is None else cov_out.data_ptr()
-        a.w_out = None if w_out is None else w_out.data_ptr()
-        fb = self._fallback_ptr(fallback, B)
-        a.fallback = fb.value if fb is not None else None
-        check(lib.avz_beamform_spectral(self._h, ct.byref(a), _stream_handle(stream)),
-              "avz_beamform_spectral")
+        a.cov_out, a.w_out = ptr(cov_out), ptr(w_out)
+        a.fallback = self._fallback_ptr(fallback, B, dev)
+        A.call("avz_beamform_spectral", self._h, ct.byref(a), stream=stream)
         return S
 
     def istft(self, S: torch.Tensor, *, out=None, peak=None, workspace=None, stream=None):
         """scipy.signal.istft(S, nperseg=n_fft, noverlap=n_fft/2) of S [B, F, T] complex64
-        (t contiguous): (out [B, >= (T-1) hop], peak [B]); the plan's normalisation applies."""
-        if S.dtype != torch.complex64 or S.dim() != 3 or S.shape[1] != self.F or S.stride(2) != 1 \
-                or not S.is_cuda:
-            raise ValueError(f"S must be complex64 [B, {self.F}, T] (t contiguous) on the device")
+        (t contiguous): (out [B, >= (T - 1) hop], peak [B]); the plan's normalisation applies."""
+        tensor("S", S, C64, (None, self.F, None), "cuda")
         B, _, T = S.shape
+        dev = S.device
         n = (T - 1) * self.hop
         if out is None:
-            out = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=S.device)
+            out = torch.empty((B, (n + 3) // 4 * 4), dtype=torch.float32, device=dev)
+        else:
+            tensor("out", out, F32, (ge(B), ge(n)), dev)
         if peak is None:
-            peak = torch.empty((B,), dtype=torch.float32, device=S.device)
-        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B or out.shape[1] < n \
-                or out.stride(1) != 1:
-            raise ValueError("out must be float32 [>= B, >= (T - 1) hop]")
-        wp, wn = (None, 0) if workspace is None else (ct.c_void_p(workspace.data_ptr()),
-                                                       workspace.numel())
-        check(lib.avz_istft(self._h, B, T, ct.c_void_p(S.data_ptr()), S.stride(0), S.stride(1),
-                            ct.c_void_p(out.data_ptr()), out.stride(0),
-                            ct.c_void_p(peak.data_ptr()), wp, wn, _stream_handle(stream)),
-              "avz_istft")
+            peak = torch.empty((B,), dtype=torch.float32, device=dev)
+        else:
+            tensor("peak", peak, F32, ge(B), dev, ANY)
+        if workspace is not None:
+            tensor("workspace", workspace, U8, ge(0), dev, ANY)
+        A.call("avz_istft", self._h, B, T, ptr(S), S.stride(0), S.stride(1), ptr(out),
+               out.stride(0), ptr(peak), ptr(workspace),
+               0 if workspace is None else workspace.numel(), stream=stream)
         return out, peak
 
     def stft(self, x: torch.Tensor, lengths: torch.Tensor | None = None, max_len=None,
              stream=None) -> torch.Tensor:
         """scipy.signal.stft(x, fs, nperseg=n_fft, noverlap=n_fft//2) for x [B, C, S]
         (C in {1, 2}); returns complex64 [B, C, F, T]."""
-        if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1 or not x.is_cuda:
-            raise ValueError("x must be float32 [B, C, S] on the device")
+        tensor("x", x, F32, (None, None, None), "cuda")
         B, Cn, S = x.shape
-        if lengths is None:
-            lengths = torch.full((B,), S, dtype=torch.int32, device=x.device)
-            max_len = S
-        if max_len is None:
-            max_len = int(lengths.max().item())
+        lengths, max_len = A.lengths(lengths, max_len, B, S, x.device)
         T = n_frames(max_len, self.hop)
         Y = torch.zeros((B, Cn, self.F, T), dtype=torch.complex64, device=x.device)
-        check(lib.avz_stft(self._h, B, Cn, ct.c_void_p(lengths.data_ptr()), int(max_len),
-                           ct.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
-                           ct.c_void_p(Y.data_ptr()), Y.stride(0), Y.stride(1), Y.stride(2),
-                           _stream_handle(stream)), "avz_stft")
+        A.call("avz_stft", self._h, B, Cn, ptr(lengths), max_len, ptr(x), x.stride(0),
+               x.stride(1), ptr(Y), Y.stride(0), Y.stride(1), Y.stride(2), stream=stream)
         return Y
 
 
@@ -409,30 +362,11 @@ def mask_features(plan: MVDRPlan, x: torch.Tensor, layout: str = "unet", lengths
                        (full_audio_generating_pipeline/inference.py:90-94);
     layout "tflite" -> [B, F, T, 4]: log_mag, sin(ipd), cos(ipd), linspace(0, 1, F)
                        (Final_pipeline/src/inference.py:198-203, 117-128)."""
-    if x.dim() != 3 or x.shape[1] != 2 or x.dtype != torch.float32 or x.stride(2) != 1 \
-            or not x.is_cuda:
-        raise ValueError("x must be float32 [B, 2, S] on the device")
-    B, _, S = x.shape
-    if lengths is None:
-        lengths = torch.full((B,), S, dtype=torch.int32, device=x.device)
-        max_len = S
-    if max_len is None:
-        max_len = int(lengths.max().item())
-    T = n_frames(max_len, plan.hop)
-    F = plan.F
-    if layout == "unet":
-        out = torch.zeros((B, 2, F, T), dtype=torch.float32, device=x.device)
-        sb, sc, sf, st = out.stride()
-    elif layout == "tflite":
-        out = torch.zeros((B, F, T, 4), dtype=torch.float32, device=x.device)
-        sb, sf, st, sc = out.stride()
-    else:
-        raise ValueError(f"unknown feature layout {layout!r}")
-    check(lib.avz_mask_features(plan._h, FEATURE_LAYOUTS[layout], B,
-                                ct.c_void_p(lengths.data_ptr()), int(max_len),
-                                ct.c_void_p(x.data_ptr()), x.stride(0), x.stride(1),
-                                ct.c_void_p(out.data_ptr()), sb, sc, sf, st,
-                                _stream_handle(stream)), "avz_mask_features")
+    B, S, dev = A.mic_pair("x", x)
+    lengths, max_len = A.lengths(lengths, max_len, B, S, dev)
+    out, strides = A.features(layout, B, plan.F, n_frames(max_len, plan.hop), dev)
+    A.call("avz_mask_features", plan._h, FEATURE_LAYOUTS[layout], B, ptr(lengths), max_len,
+           ptr(x), x.stride(0), x.stride(1), ptr(out), *strides, stream=stream)
     return out
 
 
@@ -444,46 +378,53 @@ def mask_training_batch(plan: MVDRPlan, mix: torch.Tensor, tgt: torch.Tensor, it
     where |STFT(tgt)| > |STFT(itf)| on the kernel's fp32 transforms, else 0.0
     (full_audio_generating_pipeline/model_training.py:80-92). Frames past an item's length
     stay 0."""
-    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or mix.stride(2) != 1 \
-            or not mix.is_cuda:
-        raise ValueError("mix must be float32 [B, 2, S] on the device")
-    B, _, S = mix.shape
-    for name, r in (("tgt", tgt), ("itf", itf)):
-        if r.dim() != 2 or tuple(r.shape) != (B, S) or r.dtype != torch.float32 \
-                or r.stride(1) != 1 or r.device != mix.device:
-            raise ValueError(f"{name} must be float32 [{B}, {S}] on the mixture's device")
+    B, S, dev = A.mic_pair("mix", mix)
+    tensor("tgt", tgt, F32, (B, S), dev)
+    tensor("itf", itf, F32, (B, S), dev)
     if itf.stride(0) != tgt.stride(0):
+        # the kernel takes one row stride for both: copies here, where stream_push raises
         itf = itf.contiguous()
         tgt = tgt.contiguous()
-    if lengths is None:
-        lengths = torch.full((B,), S, dtype=torch.int32, device=mix.device)
-        max_len = S
-    if max_len is None:
-        max_len = int(lengths.max().item())
+    lengths, max_len = A.lengths(lengths, max_len, B, S, dev)
     T = n_frames(max_len, plan.hop)
-    F = plan.F
-    if layout == "unet":
-        feat = torch.zeros((B, 2, F, T), dtype=torch.float32, device=mix.device)
-        sb, sc, sf, st = feat.stride()
-    elif layout == "tflite":
-        feat = torch.zeros((B, F, T, 4), dtype=torch.float32, device=mix.device)
-        sb, sf, st, sc = feat.stride()
-    else:
-        raise ValueError(f"unknown feature layout {layout!r}")
-    label = torch.zeros((B, F, T), dtype=torch.float32, device=mix.device)
-    check(lib.avz_mask_training_batch(
-        plan._h, FEATURE_LAYOUTS[layout], B, ct.c_void_p(lengths.data_ptr()), int(max_len),
-        ct.c_void_p(mix.data_ptr()), mix.stride(0), mix.stride(1),
-        ct.c_void_p(tgt.data_ptr()), ct.c_void_p(itf.data_ptr()), tgt.stride(0),
-        ct.c_void_p(feat.data_ptr()), sb, sc, sf, st,
-        ct.c_void_p(label.data_ptr()), label.stride(0), label.stride(1), label.stride(2),
-        _stream_handle(stream)), "avz_mask_training_batch")
+    feat, strides = A.features(layout, B, plan.F, T, dev)
+    label = torch.zeros((B, plan.F, T), dtype=torch.float32, device=dev)
+    A.call("avz_mask_training_batch", plan._h, FEATURE_LAYOUTS[layout], B, ptr(lengths), max_len,
+           ptr(mix), mix.stride(0), mix.stride(1), ptr(tgt), ptr(itf), tgt.stride(0),
+           ptr(feat), *strides, ptr(label), *label.stride(), stream=stream)
     return feat, label
 
 
-# ------------------------------------------------------------------ streaming causal MVDR
-# Thin wrappers over avz_stream_* (include/avz.h); avz/stream.py StreamingBeamformer owns the
-# state buffer and is the interface to use.
+# ------------------------------------------------------------------ streaming entry points
+# Thin wrappers over avz_stream_* (causal MVDR), avz_wpe_stream_* (online WPE) and
+# avz_delay_stream_* (blind delay mask; include/avz.h). avz/stream.py StreamingBeamformer and
+# StreamingDelayMask and avz/dereverb.py StreamingWPE own the state buffers and are the
+# interfaces to use.
+def _state_args(state, streams, select, name="select", dtype=I32):
+    """(state pointer, its bytes, streams, select pointer) of a *_stream_reset / _steer:
+    state a uint8 device buffer, select (or the angles) one entry per stream on its device."""
+    tensor("state", state, U8, ge(0), "cuda", ANY)
+    if select is not None:
+        tensor(name, select, dtype, ge(int(streams)), state.device, ANY)
+    return ptr(state), state.numel(), int(streams), ptr(select)
+
+
+def _push_args(a, plan, state, mix, forget, active, adapt):
+    """Fill what every *_stream_push takes of a hop block (streams, hops, forget, flags, mix,
+    state): returns (streams, hops, the block's device)."""
+    streams, hops = A.hop_block(mix, plan.hop)
+    dev = mix.device
+    tensor("state", state, U8, ge(0), dev, ANY)
+    for name, t in (("active", active), ("adapt", adapt)):
+        if t is not None:
+            tensor(name, t, I32, ge(streams), dev, ANY)
+    a.streams, a.hops, a.forget = streams, hops, float(forget)
+    a.active, a.adapt = ptr(active), ptr(adapt)
+    a.mix, a.mix_stride, a.ch_stride = ptr(mix), mix.stride(0), mix.stride(1)
+    a.state, a.state_bytes = ptr(state), state.numel()
+    return streams, hops, dev
+
+
 def stream_state_bytes(plan: MVDRPlan, streams: int) -> int:
     return check(lib.avz_stream_state_bytes(plan._h, int(streams)), "avz_stream_state_bytes")
 
@@ -491,15 +432,14 @@ def stream_state_bytes(plan: MVDRPlan, streams: int) -> int:
 def stream_reset(plan: MVDRPlan, state: torch.Tensor, streams: int, select=None, stream=None):
     """Zero the selected streams (select: int32 [streams] device tensor, None = all) and give
     them the plan's steering table."""
-    check(lib.avz_stream_reset(plan._h, _ptr(state), state.numel(), int(streams), _ptr(select),
-                               _stream_handle(stream)), "avz_stream_reset")
+    A.call("avz_stream_reset", plan._h, *_state_args(state, streams, select), stream=stream)
 
 
 def stream_steer(plan: MVDRPlan, state: torch.Tensor, streams: int, angles: torch.Tensor,
                  stream=None):
     """angles: float64 [streams] device tensor, degrees; NaN keeps a stream's direction."""
-    check(lib.avz_stream_steer(plan._h, _ptr(state), state.numel(), int(streams), _ptr(angles),
-                               _stream_handle(stream)), "avz_stream_steer")
+    A.call("avz_stream_steer", plan._h, *_state_args(state, streams, angles, "angles", F64),
+           stream=stream)
 
 
 def stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out: torch.Tensor, *,
@@ -510,47 +450,30 @@ def stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out: tor
     ref_int [streams, hops * hop] sharing a row stride (IBM plans); active / adapt int32
     [streams]; w_out [streams, F, 4] float32, cov_out [streams, F, 5] float64 and mask_out
     [streams, F, hops] float32 contiguous."""
-    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or \
-            mix.stride(2) != 1 or not mix.is_cuda:
-        raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
-    streams, _, n = mix.shape
-    if n == 0 or n % plan.hop:
-        raise ValueError("mix must hold a whole number (>= 1) of hops")
-    hops = n // plan.hop
-    if out.dtype != torch.float32 or tuple(out.shape) != (streams, n) or out.stride(1) != 1:
-        raise ValueError("out must be float32 [streams, hops * hop]")
     a = AvzStreamArgs()
-    a.streams, a.hops, a.forget = streams, hops, float(forget)
-    a.active, a.adapt = _ptr(active), _ptr(adapt)
-    a.mix, a.mix_stride, a.ch_stride = _ptr(mix), mix.stride(0), mix.stride(1)
+    streams, hops, dev = _push_args(a, plan, state, mix, forget, active, adapt)
+    n, F = hops * plan.hop, plan.F
+    tensor("out", out, F32, (streams, n), dev)
     if ref_tgt is not None or ref_int is not None:
         for name, r in (("ref_tgt", ref_tgt), ("ref_int", ref_int)):
-            if r is None or tuple(r.shape) != (streams, n) or r.dtype != torch.float32 or \
-                    r.stride(1) != 1:
-                raise ValueError(f"{name} must be float32 [streams, hops * hop]")
+            if r is None:
+                raise ValueError(f"{name} must be given with the other reference")
+            tensor(name, r, F32, (streams, n), dev)
         if ref_int.stride(0) != ref_tgt.stride(0):
             raise ValueError("ref_tgt and ref_int must share a stride")
-        a.ref_tgt, a.ref_int, a.ref_stride = _ptr(ref_tgt), _ptr(ref_int), ref_tgt.stride(0)
+        a.ref_tgt, a.ref_int, a.ref_stride = ptr(ref_tgt), ptr(ref_int), ref_tgt.stride(0)
     if mask is not None:
-        if tuple(mask.shape) != (streams, plan.F, hops) or mask.dtype != torch.float32:
-            raise ValueError("mask must be float32 [streams, F, hops]")
-        a.ext_mask = _ptr(mask)
+        tensor("mask", mask, F32, (streams, F, hops), dev, ANY)
+        a.ext_mask = ptr(mask)
         a.mask_stride_b, a.mask_stride_f, a.mask_stride_t = mask.stride()
-    a.out, a.out_stride = _ptr(out), out.stride(0)
-    for name, t, shape, dt in (("w_out", w_out, (streams, plan.F, 4), torch.float32),
-                               ("cov_out", cov_out, (streams, plan.F, 5), torch.float64),
-                               ("mask_out", mask_out, (streams, plan.F, hops), torch.float32)):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}")
-    a.w_out, a.cov_out, a.mask_out = _ptr(w_out), _ptr(cov_out), _ptr(mask_out)
-    a.state, a.state_bytes = _ptr(state), state.numel()
-    check(lib.avz_stream_push(plan._h, ct.byref(a), _stream_handle(stream)), "avz_stream_push")
+    a.out, a.out_stride = ptr(out), out.stride(0)
+    A.outputs((("w_out", w_out, (streams, F, 4), F32), ("cov_out", cov_out, (streams, F, 5), F64),
+               ("mask_out", mask_out, (streams, F, hops), F32)), dev)
+    a.w_out, a.cov_out, a.mask_out = ptr(w_out), ptr(cov_out), ptr(mask_out)
+    A.call("avz_stream_push", plan._h, ct.byref(a), stream=stream)
     return out
 
 
-# ------------------------------------------------------------------ streaming online WPE
-# Thin wrappers over avz_wpe_stream_* (include/avz.h); avz/dereverb.py StreamingWPE owns the
-# state buffer and is the interface to use.
 def wpe_stream_state_bytes(plan: MVDRPlan, streams: int, taps: int = 10, delay: int = 3) -> int:
     return check(lib.avz_wpe_stream_state_bytes(plan._h, int(streams), int(taps), int(delay)),
                  "avz_wpe_stream_state_bytes")
@@ -560,9 +483,9 @@ def wpe_stream_reset(plan: MVDRPlan, state: torch.Tensor, streams: int, taps: in
                      delay: int = 3, q_init: float = 1.0, select=None, stream=None):
     """Start the selected streams (select: int32 [streams] device tensor, None = all): zero
     history, G = 0, Q = q_init I; fixes the buffer's taps and delay."""
-    check(lib.avz_wpe_stream_reset(plan._h, _ptr(state), state.numel(), int(streams), int(taps),
-                                   int(delay), float(q_init), _ptr(select),
-                                   _stream_handle(stream)), "avz_wpe_stream_reset")
+    p, nbytes, streams, sel = _state_args(state, streams, select)
+    A.call("avz_wpe_stream_reset", plan._h, p, nbytes, streams, int(taps), int(delay),
+           float(q_init), sel, stream=stream)
 
 
 def wpe_stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out: torch.Tensor, *,
@@ -572,31 +495,16 @@ def wpe_stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, out:
     """One avz_wpe_stream_push: mix [streams, 2, hops * hop] -> out of the same shape (float32
     device tensors, samples contiguous). active / adapt int32 [streams]; Y_out / Z_out
     complex64 [streams, 2, F, hops] and G_out complex128 [streams, F, 2 taps, 2], contiguous."""
-    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or \
-            mix.stride(2) != 1 or not mix.is_cuda:
-        raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
-    streams, _, n = mix.shape
-    if n == 0 or n % plan.hop:
-        raise ValueError("mix must hold a whole number (>= 1) of hops")
-    hops = n // plan.hop
-    if out.dtype != torch.float32 or tuple(out.shape) != (streams, 2, n) or out.stride(2) != 1:
-        raise ValueError("out must be float32 [streams, 2, hops * hop]")
     a = _lib.AvzWpeStreamArgs()
-    a.streams, a.hops, a.taps, a.delay = streams, hops, int(taps), int(delay)
-    a.forget, a.power_floor = float(forget), float(power_floor)
-    a.active, a.adapt = _ptr(active), _ptr(adapt)
-    a.mix, a.mix_stride, a.ch_stride = _ptr(mix), mix.stride(0), mix.stride(1)
-    a.out, a.out_stride, a.out_ch_stride = _ptr(out), out.stride(0), out.stride(1)
-    for name, t, shape, dt in (("Y_out", Y_out, (streams, 2, plan.F, hops), torch.complex64),
-                               ("Z_out", Z_out, (streams, 2, plan.F, hops), torch.complex64),
-                               ("G_out", G_out, (streams, plan.F, 2 * int(taps), 2),
-                                torch.complex128)):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}")
-    a.Y_out, a.Z_out, a.G_out = _ptr(Y_out), _ptr(Z_out), _ptr(G_out)
-    a.state, a.state_bytes = _ptr(state), state.numel()
-    check(lib.avz_wpe_stream_push(plan._h, ct.byref(a), _stream_handle(stream)),
-          "avz_wpe_stream_push")
+    streams, hops, dev = _push_args(a, plan, state, mix, forget, active, adapt)
+    tensor("out", out, F32, (streams, 2, hops * plan.hop), dev)
+    a.taps, a.delay, a.power_floor = int(taps), int(delay), float(power_floor)
+    a.out, a.out_stride, a.out_ch_stride = ptr(out), out.stride(0), out.stride(1)
+    A.outputs((("Y_out", Y_out, (streams, 2, plan.F, hops), C64),
+               ("Z_out", Z_out, (streams, 2, plan.F, hops), C64),
+               ("G_out", G_out, (streams, plan.F, 2 * int(taps), 2), C128)), dev)
+    a.Y_out, a.Z_out, a.G_out = ptr(Y_out), ptr(Z_out), ptr(G_out)
+    A.call("avz_wpe_stream_push", plan._h, ct.byref(a), stream=stream)
     return out
 
 
@@ -605,6 +513,13 @@ def delay_mask_workspace_bytes(plan: MVDRPlan, batch: int, max_len: int,
     return check(lib.avz_delay_mask_workspace_bytes(plan._h, int(batch), int(max_len),
                                                     int(hist_bins)),
                  "avz_delay_mask_workspace_bytes")
+
+
+def _delay_params(a, angles, hist_bins, smooth, rel_height, min_sep, max_peaks, f_lo):
+    """The histogram and peak-picking fields avz_delay_mask and avz_delay_stream_push share."""
+    a.angle_deg = ptr(angles)
+    a.hist_bins, a.smooth, a.max_peaks = int(hist_bins), int(smooth), int(max_peaks)
+    a.rel_height, a.min_sep, a.f_lo_hz = float(rel_height), float(min_sep), float(f_lo)
 
 
 def delay_mask(plan: MVDRPlan, mix: torch.Tensor, lengths=None, angles=None, *, hist_bins=65,
@@ -620,59 +535,43 @@ def delay_mask(plan: MVDRPlan, mix: torch.Tensor, lengths=None, angles=None, *, 
     is allocated otherwise). With ``return_debug`` also returns hist [B, hist_bins] float64
     (before smoothing), delays [B, 8] float64 (delta_t, the kept delays, NaN) and n_peaks [B]
     int32 (-1: row shorter than n_fft)."""
-    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or mix.stride(2) != 1 \
-            or not mix.is_cuda:
-        raise ValueError("mix must be float32 [B, 2, S] on the device")
-    B, _, S = mix.shape
-    dev = mix.device
-    if lengths is None:
-        lengths = torch.full((B,), S, dtype=torch.int32, device=dev)
-        max_len = S
-    if lengths.dtype != torch.int32 or lengths.device != dev or not lengths.is_contiguous():
-        raise ValueError("lengths must be a contiguous int32 [B] tensor on the mixture's device")
-    if max_len is None:
-        max_len = int(lengths.max().item())
-    if angles is not None and (angles.dtype != torch.float64 or angles.numel() < B
-                               or not angles.is_contiguous() or angles.device != dev):
-        raise ValueError("angles must be a contiguous float64 [B] tensor on the mixture's device")
-    T = n_frames(int(max_len), plan.hop)
+    B, S, dev = A.mic_pair("mix", mix)
+    lengths, max_len = A.lengths(lengths, max_len, B, S, dev, FULL)
+    if angles is not None:
+        tensor("angles", angles, F64, ge(B), dev, FULL)
+    T = n_frames(max_len, plan.hop)
     if mask is None:
+        # a new batch mask starts as zeros: the kernel leaves frames past a row's own count
         mask = torch.zeros((B, plan.F, T), dtype=torch.float32, device=dev)
-    if mask.dtype != torch.float32 or mask.dim() != 3 or mask.shape[0] != B \
-            or mask.shape[1] < plan.F or mask.shape[2] < T or mask.device != dev:
-        raise ValueError(f"mask must be float32 [{B}, >= {plan.F}, >= {T}] on the mixture's device")
+    else:
+        tensor("mask", mask, F32, (B, ge(plan.F), ge(T)), dev, ANY)
     ws = workspace
     if ws is None:
+        # this wrapper allocates its own workspace and keeps it alive on the call's stream
         ws = torch.empty(delay_mask_workspace_bytes(plan, B, max_len, hist_bins),
                          dtype=torch.uint8, device=dev)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
-        raise ValueError("workspace must be a contiguous uint8 tensor on the mixture's device")
+    else:
+        tensor("workspace", ws, U8, ge(0), dev, FULL)
     a = _lib.AvzDelayMaskArgs()
-    a.batch, a.len, a.max_len = B, lengths.data_ptr(), int(max_len)
-    a.mix, a.mix_stride, a.ch_stride = mix.data_ptr(), mix.stride(0), mix.stride(1)
-    a.angle_deg = None if angles is None else angles.data_ptr()
-    a.hist_bins, a.smooth, a.max_peaks = int(hist_bins), int(smooth), int(max_peaks)
-    a.rel_height, a.min_sep, a.f_lo_hz = float(rel_height), float(min_sep), float(f_lo)
-    a.mask = mask.data_ptr()
+    a.batch, a.len, a.max_len = B, ptr(lengths), max_len
+    a.mix, a.mix_stride, a.ch_stride = ptr(mix), mix.stride(0), mix.stride(1)
+    _delay_params(a, angles, hist_bins, smooth, rel_height, min_sep, max_peaks, f_lo)
+    a.mask = ptr(mask)
     a.mask_stride_b, a.mask_stride_f, a.mask_stride_t = mask.stride()
     hist = delays = n_peaks = None
     if return_debug:
         hist = torch.zeros((B, int(hist_bins)), dtype=torch.float64, device=dev)
         delays = torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev)
         n_peaks = torch.zeros(B, dtype=torch.int32, device=dev)
-        a.hist_out, a.delays_out, a.n_peaks = hist.data_ptr(), delays.data_ptr(), n_peaks.data_ptr()
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    with torch.cuda.device(dev):
-        check(lib.avz_delay_mask(plan._h, ct.byref(a), _stream_handle(stream)), "avz_delay_mask")
+        a.hist_out, a.delays_out, a.n_peaks = ptr(hist), ptr(delays), ptr(n_peaks)
+    a.workspace, a.workspace_bytes = ptr(ws), ws.numel()
+    A.call("avz_delay_mask", plan._h, ct.byref(a), stream=stream, device=dev)
     if workspace is None:
         ws.record_stream(stream if stream is not None else torch.cuda.current_stream(dev))
     out = mask[:, :plan.F, :T]
     return (out, hist, delays, n_peaks) if return_debug else out
 
 
-# ------------------------------------------------------------------ streaming blind delay mask
-# Thin wrappers over avz_delay_stream_* (include/avz.h); avz/stream.py StreamingDelayMask owns
-# the state buffer and is the interface to use.
 def delay_stream_state_bytes(plan: MVDRPlan, streams: int, hist_bins: int = 65) -> int:
     return check(lib.avz_delay_stream_state_bytes(plan._h, int(streams), int(hist_bins)),
                  "avz_delay_stream_state_bytes")
@@ -682,9 +581,9 @@ def delay_stream_reset(plan: MVDRPlan, state: torch.Tensor, streams: int, hist_b
                        select=None, stream=None):
     """Start the selected streams (select: int32 [streams] device tensor, None = all): zero
     history, h = 0; fixes the buffer's hist_bins."""
-    check(lib.avz_delay_stream_reset(plan._h, _ptr(state), state.numel(), int(streams),
-                                     int(hist_bins), _ptr(select), _stream_handle(stream)),
-          "avz_delay_stream_reset")
+    p, nbytes, streams, sel = _state_args(state, streams, select)
+    A.call("avz_delay_stream_reset", plan._h, p, nbytes, streams, int(hist_bins), sel,
+           stream=stream)
 
 
 def delay_stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, mask=None, *,
@@ -696,40 +595,23 @@ def delay_stream_push(plan: MVDRPlan, state: torch.Tensor, mix: torch.Tensor, ma
     beamformer's push of the same hops takes. angles float64 [streams] (NaN = the plan's);
     active / adapt int32 [streams]; hist_out [streams, hist_bins] float64, delays_out
     [streams, hops, 8] float64 and n_peaks [streams, hops] int32, contiguous."""
-    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or \
-            mix.stride(2) != 1 or not mix.is_cuda:
-        raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
-    streams, _, n = mix.shape
-    if n == 0 or n % plan.hop:
-        raise ValueError("mix must hold a whole number (>= 1) of hops")
-    hops = n // plan.hop
-    if mask is None:
-        mask = torch.ones((streams, plan.F, hops), dtype=torch.float32, device=mix.device)
-    if tuple(mask.shape) != (streams, plan.F, hops) or mask.dtype != torch.float32 or \
-            mask.device != mix.device:
-        raise ValueError("mask must be float32 [streams, F, hops] on the mixture's device")
-    if angles is not None and (angles.dtype != torch.float64 or tuple(angles.shape) != (streams,)
-                               or not angles.is_contiguous() or angles.device != mix.device):
-        raise ValueError("angles must be a contiguous float64 [streams] tensor on the device")
     a = _lib.AvzDelayStreamArgs()
-    a.streams, a.hops, a.forget = streams, hops, float(forget)
-    a.active, a.adapt = _ptr(active), _ptr(adapt)
-    a.mix, a.mix_stride, a.ch_stride = _ptr(mix), mix.stride(0), mix.stride(1)
-    a.angle_deg = _ptr(angles)
-    a.hist_bins, a.smooth, a.max_peaks = int(hist_bins), int(smooth), int(max_peaks)
-    a.rel_height, a.min_sep, a.f_lo_hz = float(rel_height), float(min_sep), float(f_lo)
-    a.mask = _ptr(mask)
+    streams, hops, dev = _push_args(a, plan, state, mix, forget, active, adapt)
+    if mask is None:
+        # a new streaming mask starts as ones (all target): inactive streams keep that
+        mask = torch.ones((streams, plan.F, hops), dtype=torch.float32, device=dev)
+    else:
+        tensor("mask", mask, F32, (streams, plan.F, hops), dev, ANY)
+    if angles is not None:
+        tensor("angles", angles, F64, (streams,), dev, FULL)
+    _delay_params(a, angles, hist_bins, smooth, rel_height, min_sep, max_peaks, f_lo)
+    a.mask = ptr(mask)
     a.mask_stride_b, a.mask_stride_f, a.mask_stride_t = mask.stride()
-    for name, t, shape, dt in (("hist_out", hist_out, (streams, int(hist_bins)), torch.float64),
-                               ("delays_out", delays_out, (streams, hops, 8), torch.float64),
-                               ("n_peaks", n_peaks, (streams, hops), torch.int32)):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape}")
-    a.hist_out, a.delays_out, a.n_peaks = _ptr(hist_out), _ptr(delays_out), _ptr(n_peaks)
-    a.state, a.state_bytes = _ptr(state), state.numel()
-    with torch.cuda.device(mix.device):
-        check(lib.avz_delay_stream_push(plan._h, ct.byref(a), _stream_handle(stream)),
-              "avz_delay_stream_push")
+    A.outputs((("hist_out", hist_out, (streams, int(hist_bins)), F64),
+               ("delays_out", delays_out, (streams, hops, 8), F64),
+               ("n_peaks", n_peaks, (streams, hops), I32)), dev)
+    a.hist_out, a.delays_out, a.n_peaks = ptr(hist_out), ptr(delays_out), ptr(n_peaks)
+    A.call("avz_delay_stream_push", plan._h, ct.byref(a), stream=stream, device=dev)
     return mask
 
 
@@ -737,20 +619,12 @@ def srp_scan(plan: MVDRPlan, mix: torch.Tensor, lengths=None, max_len=None, n_an
              angle_lo=0.0, angle_hi=180.0, f_lo=200.0, f_hi=4000.0, stream=None):
     """scripts/debug_srp.py:46-62 for a [B, 2, S] batch -> power map [B, n_angles] in dB
     relative to each utterance's maximum (float64, device)."""
-    if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32 or not mix.is_cuda \
-            or mix.stride(2) != 1:
-        raise ValueError("mix must be float32 [B, 2, S] on the device")
-    B, _, S = mix.shape
-    if lengths is None:
-        lengths = torch.full((B,), S, dtype=torch.int32, device=mix.device)
-        max_len = S
-    if max_len is None:
-        max_len = int(lengths.max().item())
-    out = torch.empty((B, n_angles), dtype=torch.float64, device=mix.device)
-    check(lib.avz_srp_scan(plan._h, B, ct.c_void_p(lengths.data_ptr()), int(max_len),
-                           ct.c_void_p(mix.data_ptr()), mix.stride(0), mix.stride(1), n_angles,
-                           float(angle_lo), float(angle_hi), float(f_lo), float(f_hi),
-                           ct.c_void_p(out.data_ptr()), _stream_handle(stream)), "avz_srp_scan")
+    B, S, dev = A.mic_pair("mix", mix)
+    lengths, max_len = A.lengths(lengths, max_len, B, S, dev)
+    out = torch.empty((B, n_angles), dtype=torch.float64, device=dev)
+    A.call("avz_srp_scan", plan._h, B, ptr(lengths), max_len, ptr(mix), mix.stride(0),
+           mix.stride(1), n_angles, float(angle_lo), float(angle_hi), float(f_lo), float(f_hi),
+           ptr(out), stream=stream)
     return out
 
 
@@ -760,32 +634,24 @@ def wpe_spectral(Y: torch.Tensor, taps: int = 10, delay: int = 3, iterations: in
     (avz_wpe_spectral; rt_av_zoom/core/dereverb.py:76-78 per item). ``frames``: optional
     int32 [B] valid frames per item (frames beyond it are copied); ``out`` may be Y itself;
     ``status``: optional int32 [B, F] (0 dereverberated, 1 / 2 passed through)."""
-    if Y.dtype != torch.complex64 or Y.dim() != 4 or Y.shape[1] != 2 or Y.stride(3) != 1 \
-            or not Y.is_cuda:
-        raise ValueError("Y must be complex64 [B, 2, F, T] (t contiguous) on the device")
+    tensor("Y", Y, C64, (None, 2, None, None), "cuda")
     B, _, F, T = Y.shape
+    dev = Y.device
     if out is None:
-        out = torch.empty((B, 2, F, T), dtype=torch.complex64, device=Y.device)
-    if out.dtype != torch.complex64 or tuple(out.shape) != (B, 2, F, T) or out.stride(3) != 1 \
-            or out.device != Y.device:
-        raise ValueError("out must be complex64 [B, 2, F, T] (t contiguous) on Y's device")
-    if frames is not None and (frames.dtype != torch.int32 or frames.numel() < B
-                               or not frames.is_contiguous() or frames.device != Y.device):
-        raise ValueError("frames must be a contiguous int32 [B] tensor on Y's device")
-    if status is not None and (status.dtype != torch.int32 or status.numel() < B * F
-                               or not status.is_contiguous() or status.device != Y.device):
-        raise ValueError("status must be a contiguous int32 [B, F] tensor on Y's device")
+        out = torch.empty((B, 2, F, T), dtype=torch.complex64, device=dev)
+    else:
+        tensor("out", out, C64, (B, 2, F, T), dev)
+    A.outputs((("frames", frames, ge(B), I32), ("status", status, ge(B * F), I32)), dev)
     a = _lib.AvzWpeArgs()
     a.batch, a.bins, a.frames = B, F, T
-    a.frames_b = None if frames is None else frames.data_ptr()
+    a.frames_b = ptr(frames)
     a.taps, a.delay, a.iterations = int(taps), int(delay), int(iterations)
-    a.Y = Y.data_ptr()
+    a.Y = ptr(Y)
     a.y_stride_b, a.y_stride_m, a.y_stride_f = Y.stride(0), Y.stride(1), Y.stride(2)
-    a.Z = out.data_ptr()
+    a.Z = ptr(out)
     a.z_stride_b, a.z_stride_m, a.z_stride_f = out.stride(0), out.stride(1), out.stride(2)
-    a.status = None if status is None else status.data_ptr()
-    with torch.cuda.device(Y.device):
-        check(lib.avz_wpe_spectral(ct.byref(a), _stream_handle(stream)), "avz_wpe_spectral")
+    a.status = ptr(status)
+    A.call("avz_wpe_spectral", ct.byref(a), stream=stream, device=dev)
     return out
 
 
@@ -801,18 +667,12 @@ def room_rir(room, src_pos, device=None, out=None, stream=None) -> torch.Tensor:
     if not isinstance(src_pos, torch.Tensor):
         dev = device or torch.device("cuda", torch.cuda.current_device())
         src_pos = torch.as_tensor(np.asarray(src_pos, np.float64)).to(dev)
-    if src_pos.dtype != torch.float64 or src_pos.dim() != 3 or src_pos.shape[2] != 3 \
-            or not src_pos.is_cuda:
-        raise ValueError("src_pos must be float64 [B, S, 3] on the device")
-    src_pos = src_pos.contiguous()
+    src_pos = tensor("src_pos", src_pos, F64, (None, None, 3), "cuda", ANY).contiguous()
     B, S, _ = src_pos.shape
+    dev = src_pos.device
     if out is None:
-        out = torch.empty((B, S, 2, L), dtype=torch.float64, device=src_pos.device)
-    if out.dtype != torch.float64 or tuple(out.shape) != (B, S, 2, L) or not out.is_contiguous() \
-            or out.device != src_pos.device:
-        raise ValueError("out must be contiguous float64 [B, S, 2, rir_len] on src_pos's device")
-    with torch.cuda.device(src_pos.device):
-        check(lib.avz_room_rir(ct.byref(r), B, S, ct.c_void_p(src_pos.data_ptr()),
-                               ct.c_void_p(out.data_ptr()), _stream_handle(stream)),
-              "avz_room_rir")
+        out = torch.empty((B, S, 2, L), dtype=torch.float64, device=dev)
+    else:
+        tensor("out", out, F64, (B, S, 2, L), dev, FULL)
+    A.call("avz_room_rir", ct.byref(r), B, S, ptr(src_pos), ptr(out), stream=stream, device=dev)
     return out

@@ -19,15 +19,14 @@ IBM mode with the x(1 - noise) post-filter) or from any caller-supplied model
 """
 from __future__ import annotations
 
-import ctypes as ct
 import os
 
 import numpy as np
 import torch
 
 from . import wavio
-from ._lib import check, lib
-from .engine import MVDRPlan, _stream_handle
+from ._args import call, ptr
+from .engine import MVDRPlan
 
 # Final_pipeline/src/config.py:14-29 and inference.py:10-12
 FS = 16000
@@ -88,13 +87,9 @@ class ChunkedHybridBeamformer:
         self.item_out_len = self.plan.out_len(chunk)
 
     def _split(self, x, utt, start, lengths, items, channels, stream):
-        check(lib.avz_chunk_split(len(utt), channels, self.chunk, ct.c_void_p(utt.data_ptr()),
-                                  ct.c_void_p(start.data_ptr()), ct.c_void_p(lengths.data_ptr()),
-                                  ct.c_void_p(x.data_ptr()), x.stride(0),
-                                  x.stride(1) if channels > 1 else 0,
-                                  ct.c_void_p(items.data_ptr()), items.stride(0),
-                                  items.stride(1) if channels > 1 else 0, stream),
-              "avz_chunk_split")
+        call("avz_chunk_split", len(utt), channels, self.chunk, ptr(utt), ptr(start), ptr(lengths),
+             ptr(x), x.stride(0), x.stride(1) if channels > 1 else 0, ptr(items), items.stride(0),
+             items.stride(1) if channels > 1 else 0, stream=stream)
 
     def run(self, mix: torch.Tensor, lengths=None, ref_tgt=None, ref_int=None, mask_fn=None,
             stream=None):
@@ -107,21 +102,20 @@ class ChunkedHybridBeamformer:
         lengths = [S] * B if lengths is None else [int(x) for x in lengths]
         utt_h, start_h, base_h = chunk_table(lengths, self.hop_c)
         n = len(utt_h)
-        st = _stream_handle(stream)
         utt = torch.from_numpy(utt_h).to(dev)
         start = torch.from_numpy(start_h).to(dev)
         base = torch.from_numpy(base_h).to(dev)
         d_len = torch.tensor(lengths, dtype=torch.int32, device=dev)
         items = torch.empty((n, 2, self.chunk), dtype=torch.float32, device=dev)
-        self._split(mix, utt, start, d_len, items, 2, st)
+        self._split(mix, utt, start, d_len, items, 2, stream)
         kw = {}
         if self.mask == "ibm":
             if ref_tgt is None or ref_int is None:
                 raise ValueError("mask='ibm' needs ref_tgt and ref_int")
             it = torch.empty((n, self.chunk), dtype=torch.float32, device=dev)
             ii = torch.empty((n, self.chunk), dtype=torch.float32, device=dev)
-            self._split(ref_tgt, utt, start, d_len, it, 1, st)
-            self._split(ref_int, utt, start, d_len, ii, 1, st)
+            self._split(ref_tgt, utt, start, d_len, it, 1, stream)
+            self._split(ref_int, utt, start, d_len, ii, 1, stream)
             kw = dict(ref_tgt=it, ref_int=ii)
         else:
             if mask_fn is None:
@@ -130,12 +124,9 @@ class ChunkedHybridBeamformer:
         item_out, _ = self.plan.run(items, **kw, stream=stream)
         y = torch.zeros((B, S), dtype=torch.float32, device=dev)
         peak = torch.empty((B,), dtype=torch.float32, device=dev)
-        check(lib.avz_chunk_merge(B, max(lengths), self.hop_c, self.item_out_len,
-                                  ct.c_void_p(d_len.data_ptr()), ct.c_void_p(base.data_ptr()),
-                                  ct.c_void_p(item_out.data_ptr()), item_out.stride(0),
-                                  ct.c_void_p(y.data_ptr()), y.stride(0),
-                                  ct.c_void_p(peak.data_ptr()), int(self.normalize),
-                                  float(self.norm_eps), st), "avz_chunk_merge")
+        call("avz_chunk_merge", B, max(lengths), self.hop_c, self.item_out_len, ptr(d_len),
+             ptr(base), ptr(item_out), item_out.stride(0), ptr(y), y.stride(0), ptr(peak),
+             int(self.normalize), float(self.norm_eps), stream=stream)
         return y, peak
 
 

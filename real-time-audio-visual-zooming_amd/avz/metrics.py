@@ -19,7 +19,6 @@ from avz.stoi.stoi_batch (metrics.py:157-160); PESQ stays 
 from __future__ import annotations
 
 import csv
-import ctypes as ct
 import datetime
 import os
 
@@ -37,33 +36,30 @@ def projection_metrics(est: torch.Tensor, tgt: torch.Tensor, itf: torch.Tensor, 
     """HIP: -> float64 [B, 4] = (OSINR, OSIR, SDR, SIR) per row, in dB. With ``est_peak``
     the rows are scored as est / (est_peak + est_eps) (an un-normalised output and its
     peak, as a NORM_NONE plan returns them), the scale applied inside the fp64 sums."""
-    from ._lib import check, lib
-    from .engine import _stream_handle
+    from ._args import call, ge, ptr as p, tensor
     est, tgt, itf = (x.float().contiguous() if x.dtype != torch.float32 or x.stride(-1) != 1
                      else x for x in (est, tgt, itf))
     if est.dim() == 1:
         est, tgt, itf = est[None], tgt[None], itf[None]
-    B, L = est.shape
+    B, L = tensor("est", est, torch.float32, (None, None), "cuda").shape
     dev = est.device
+    tensor("tgt", tgt, torch.float32, (ge(B), None), dev)
+    tensor("itf", itf, torch.float32, (ge(B), None), dev)
     if lengths is None:
         lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
     else:
         lengths = torch.as_tensor(lengths, dtype=torch.int32).to(dev)
     sums = torch.empty((B, 6), dtype=torch.float64, device=dev)
     out = torch.empty((B, 4), dtype=torch.float64, device=dev)
-    p = lambda t: ct.c_void_p(t.data_ptr())  # noqa: E731
     if est_peak is not None:
         pk = est_peak.float().contiguous()
         assert pk.numel() == B and pk.device == dev
-        check(lib.avz_projection_metrics_scaled(B, L, p(lengths), p(est), est.stride(0), p(pk),
-                                                float(est_eps), p(tgt), tgt.stride(0), p(itf),
-                                                itf.stride(0), p(sums), p(out),
-                                                _stream_handle(stream)),
-              "avz_projection_metrics_scaled")
+        call("avz_projection_metrics_scaled", B, L, p(lengths), p(est), est.stride(0), p(pk),
+             float(est_eps), p(tgt), tgt.stride(0), p(itf), itf.stride(0), p(sums), p(out),
+             stream=stream)
         return out
-    check(lib.avz_projection_metrics(B, L, p(lengths), p(est), est.stride(0), p(tgt),
-                                     tgt.stride(0), p(itf), itf.stride(0), p(sums), p(out),
-                                     _stream_handle(stream)), "avz_projection_metrics")
+    call("avz_projection_metrics", B, L, p(lengths), p(est), est.stride(0), p(tgt), tgt.stride(0),
+         p(itf), itf.stride(0), p(sums), p(out), stream=stream)
     return out
 
 

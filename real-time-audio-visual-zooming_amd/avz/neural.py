@@ -29,8 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import wavio
-from ._lib import check, lib
-from .engine import MVDRPlan, _stream_handle, mask_features
+from ._args import call, ptr
+from .engine import MVDRPlan, mask_features
 from .final_pipeline import chunk_table
 
 # full_audio_generating_pipeline/config.json (read by inference.py:15-26)
@@ -192,11 +192,9 @@ class NeuralMaskBeamformer:
         base = torch.from_numpy(base_h).to(dev)
         d_len = torch.tensor(lengths, dtype=torch.int32, device=dev)
         items = torch.empty((n, 2, self.chunk), dtype=torch.float32, device=dev)
-        check(lib.avz_chunk_split(n, 2, self.chunk, ct.c_void_p(utt.data_ptr()),
-                                  ct.c_void_p(start.data_ptr()), ct.c_void_p(d_len.data_ptr()),
-                                  ct.c_void_p(mix.data_ptr()), mix.stride(0), mix.stride(1),
-                                  ct.c_void_p(items.data_ptr()), items.stride(0), items.stride(1),
-                                  _stream_handle(stream)), "avz_chunk_split")
+        call("avz_chunk_split", n, 2, self.chunk, ptr(utt), ptr(start), ptr(d_len), ptr(mix),
+             mix.stride(0), mix.stride(1), ptr(items), items.stride(0), items.stride(1),
+             stream=stream)
         return items, lengths, d_len, base
 
     def run(self, mix: torch.Tensor, lengths=None, mask_fn=None, stream=None):
@@ -204,17 +202,14 @@ class NeuralMaskBeamformer:
         mask_fn(items) -> [n, F, T] overrides the U-Net. Returns (y [B, S], peak [B])."""
         B, _, S = mix.shape
         dev = mix.device
-        st = _stream_handle(stream)
         items, lengths, d_len, base = self.split(mix, lengths, stream)
         mask = mask_fn(items) if mask_fn is not None else self.masks(items)
         item_out = self.beamform(items, mask, stream=stream)
         y = torch.zeros((B, S), dtype=torch.float32, device=dev)
         peak = torch.empty((B,), dtype=torch.float32, device=dev)
-        check(lib.avz_chunk_merge(B, max(lengths), self.hop_c, self.item_out_len,
-                                  ct.c_void_p(d_len.data_ptr()), ct.c_void_p(base.data_ptr()),
-                                  ct.c_void_p(item_out.data_ptr()), item_out.stride(0),
-                                  ct.c_void_p(y.data_ptr()), y.stride(0),
-                                  ct.c_void_p(peak.data_ptr()), 0, 0.0, st), "avz_chunk_merge")
+        call("avz_chunk_merge", B, max(lengths), self.hop_c, self.item_out_len, ptr(d_len),
+             ptr(base), ptr(item_out), item_out.stride(0), ptr(y), y.stride(0), ptr(peak), 0, 0.0,
+             stream=stream)
         return y, peak
 
 

@@ -217,8 +217,9 @@ def stoi_batch(clean, est, lengths=None, fs=16000, stream=None, resampled=None, 
             info[b] = r["status"], r["frames"], r["kept"], r["segments"]
         return torch.from_numpy(d), torch.from_numpy(info)
 
-    from ._lib import AvzStoiArgs, check, lib
-    from .engine import _stream_handle
+    from . import _args as A
+    from ._args import ptr
+    from ._lib import AvzStoiArgs
     dev = clean.device
     clean, est = (v if v.dtype == torch.float32 and v.stride(1) == 1 else v.float().contiguous()
                   for v in (clean, est))
@@ -231,28 +232,23 @@ def stoi_batch(clean, est, lengths=None, fs=16000, stream=None, resampled=None, 
     ws = workspace
     if ws is None:
         ws = torch.empty(max(workspace_bytes(B, L, fs), 1), dtype=torch.uint8, device=dev)
-    elif ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
-        raise ValueError("workspace must be a contiguous uint8 tensor on the signals' device")
+    else:
+        A.tensor("workspace", ws, torch.uint8, A.ge(0), dev, A.FULL)
+    A.outputs((("resampled", resampled, (None, None, None), torch.float32),
+               ("tob", tob, (None, None, None, None), torch.float64)), dev)
     a = AvzStoiArgs()
     a.batch, a.max_len = B, L
-    a.len = None if lengths is None else lengths.data_ptr()
+    a.len = ptr(lengths)
     a.fs = float(fs)
-    a.clean, a.clean_stride = clean.data_ptr(), clean.stride(0)
-    a.est, a.est_stride = est.data_ptr(), est.stride(0)
-    a.stoi, a.info = d.data_ptr(), info.data_ptr()
+    a.clean, a.clean_stride = ptr(clean), clean.stride(0)
+    a.est, a.est_stride = ptr(est), est.stride(0)
+    a.stoi, a.info = ptr(d), ptr(info)
     if resampled is not None:
-        if resampled.dtype != torch.float32 or resampled.dim() != 3 or resampled.stride(2) != 1 \
-                or not resampled.is_contiguous() or resampled.device != dev:
-            raise ValueError("resampled must be a contiguous float32 [B, 2, n] device tensor")
-        a.resampled, a.res_stride = resampled.data_ptr(), resampled.shape[2]
+        a.resampled, a.res_stride = ptr(resampled), resampled.shape[2]
     if tob is not None:
-        if tob.dtype != torch.float64 or tob.dim() != 4 or not tob.is_contiguous() \
-                or tob.device != dev:
-            raise ValueError("tob must be a contiguous float64 [B, 2, 15, n] device tensor")
-        a.tob, a.tob_stride = tob.data_ptr(), tob.shape[3]
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    with torch.cuda.device(dev):
-        check(lib.avz_stoi_batch(ct.byref(a), _stream_handle(stream)), "avz_stoi_batch")
+        a.tob, a.tob_stride = ptr(tob), tob.shape[3]
+    a.workspace, a.workspace_bytes = ptr(ws), ws.numel()
+    A.call("avz_stoi_batch", ct.byref(a), stream=stream, device=dev)
     if workspace is None:
         ws.record_stream(stream if stream is not None else torch.cuda.current_stream(dev))
     return d, info

@@ -213,7 +213,50 @@ def stream_numpy(mix, *, hops_per_push=None, mask=None, ref_tgt=None, ref_int=No
 
 
 # ---------------------------------------------------------------------------- device path
-class StreamingBeamformer:
+class StreamOwner:
+    """What the objects that own a stream state buffer share: plan, streams, device, the
+    zeroed uint8 buffer of ``state_bytes(plan, streams, *size_args)`` bytes (an engine
+    ``*_state_bytes`` function), and the conversions of per-stream arguments."""
+
+    def __init__(self, plan, streams: int, device, state_bytes, *size_args):
+        import torch
+        self.plan, self.streams = plan, int(streams)
+        self.device = torch.device(device if device is not None else "cuda")
+        self.state = torch.zeros(state_bytes(plan, self.streams, *size_args), dtype=torch.uint8,
+                                 device=self.device)
+
+    def _per_stream(self, v, name, dtype):
+        import torch
+        t = torch.as_tensor(v, device=self.device).to(dtype).contiguous()
+        if tuple(t.shape) != (self.streams,):
+            raise ValueError(f"{name} must have one entry per stream")
+        return t
+
+    def _flags(self, v, name):
+        """int32 [streams] on the device of per-stream flags (None stays None)."""
+        import torch
+        return None if v is None else self._per_stream(v, name, torch.int32)
+
+    def _angles(self, angles):
+        """float64 [streams] on the device of per-stream angles in degrees."""
+        import torch
+        return self._per_stream(torch.as_tensor(angles, dtype=torch.float64), "angles",
+                                torch.float64)
+
+    def _block(self, mix):
+        """A pushed block has one row per stream (engine checks the rest)."""
+        if mix.dim() != 3 or mix.shape[0] != self.streams:
+            raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
+        return mix
+
+    def _zero_hop(self):
+        """One hop of zeros, what flush() pushes."""
+        import torch
+        return torch.zeros((self.streams, 2, self.plan.hop), dtype=torch.float32,
+                           device=self.device)
+
+
+class StreamingBeamformer(StreamOwner):
     """`streams` independent causal beamformers over one device state buffer.
 
     plan: an MVDRPlan with beamformer 'mvdr', mask 'external', 'ibm' or 'ones', postfilter
@@ -223,23 +266,12 @@ class StreamingBeamformer:
     def __init__(self, plan, streams: int, forget: float = 1.0, device=None):
         import torch
         from . import engine
-        self.plan, self.streams, self.forget = plan, int(streams), float(forget)
-        self.device = torch.device(device if device is not None else "cuda")
-        nbytes = engine.stream_state_bytes(plan, self.streams)
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        super().__init__(plan, streams, device, engine.stream_state_bytes)
+        self.forget = float(forget)
         self.w = torch.zeros((self.streams, plan.F, 4), dtype=torch.float32, device=self.device)
         self.cov = torch.zeros((self.streams, plan.F, 5), dtype=torch.float64,
                                device=self.device)
         self.reset()
-
-    def _flags(self, v, name):
-        import torch
-        if v is None:
-            return None
-        t = torch.as_tensor(v, device=self.device).to(torch.int32).contiguous()
-        if tuple(t.shape) != (self.streams,):
-            raise ValueError(f"{name} must have one entry per stream")
-        return t
 
     def reset(self, select=None, stream=None):
         """Start the selected streams (flags per stream; None = all) afresh: zero history,
@@ -250,12 +282,8 @@ class StreamingBeamformer:
 
     def steer(self, angles, stream=None):
         """New direction per stream in degrees (NaN = keep), from the next pushed frame."""
-        import torch
         from . import engine
-        a = torch.as_tensor(angles, dtype=torch.float64).to(self.device).contiguous()
-        if tuple(a.shape) != (self.streams,):
-            raise ValueError("angles must have one entry per stream")
-        engine.stream_steer(self.plan, self.state, self.streams, a, stream)
+        engine.stream_steer(self.plan, self.state, self.streams, self._angles(angles), stream)
 
     def push(self, mix, *, ref_tgt=None, ref_int=None, mask=None, active=None, adapt=None,
              out=None, mask_out=None, stream=None):
@@ -265,13 +293,13 @@ class StreamingBeamformer:
         sums after the call's last frame."""
         import torch
         from . import engine
-        if mix.dim() != 3 or mix.shape[0] != self.streams:
-            raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
+        self._block(mix)
         if out is None:
             out = torch.empty((self.streams, mix.shape[2]), dtype=torch.float32,
                               device=mix.device)
         if ref_tgt is not None and ref_int is not None and \
                 ref_int.stride(0) != ref_tgt.stride(0):
+            # engine.stream_push wants one row stride for both: copies here instead of raising
             ref_tgt, ref_int = ref_tgt.contiguous(), ref_int.contiguous()
         return engine.stream_push(self.plan, self.state, mix, out, forget=self.forget,
                                   ref_tgt=ref_tgt, ref_int=ref_int, mask=mask,
@@ -282,12 +310,11 @@ class StreamingBeamformer:
     def flush(self, **kw):
         """Push one hop of zeros (all-target mask, zero references): returns the last hop."""
         import torch
-        H, dev = self.plan.hop, self.device
-        z = torch.zeros((self.streams, 2, H), dtype=torch.float32, device=dev)
+        z = self._zero_hop()
         mode = self.plan.cfg.mask
         if mode == "external":
             kw.setdefault("mask", torch.ones((self.streams, self.plan.F, 1),
-                                             dtype=torch.float32, device=dev))
+                                             dtype=torch.float32, device=self.device))
         elif mode == "ibm":
             kw.setdefault("ref_tgt", z[:, 0])
             kw.setdefault("ref_int", z[:, 1])
@@ -331,7 +358,7 @@ def enhance_stream(y_mix, mask_fn_or_refs=None, hops_per_push: int = 1, *, n_fft
 
 
 # ---------------------------------------------------------------------------- blind device path
-class StreamingDelayMask:
+class StreamingDelayMask(StreamOwner):
     """`streams` independent streaming blind delay-histogram masks over one device state buffer
     (avz_delay_stream_push, include/avz.h). The plan supplies n_fft, fs,
     mic_d, c_sound, angle_deg and max_batch; its mask and beamformer settings play no part.
@@ -347,18 +374,13 @@ class StreamingDelayMask:
         unknown = set(mask_kw) - (set(DEFAULTS) - {"hist_bins"})
         if unknown:
             raise TypeError(f"unknown mask options {sorted(unknown)}")
-        self.plan, self.streams, self.forget = plan, int(streams), float(forget)
-        self.hist_bins, self.mask_kw = int(hist_bins), dict(mask_kw)
-        self.device = torch.device(device if device is not None else "cuda")
-        nbytes = engine.delay_stream_state_bytes(plan, self.streams, self.hist_bins)
-        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self.forget, self.hist_bins, self.mask_kw = float(forget), int(hist_bins), dict(mask_kw)
+        super().__init__(plan, streams, device, engine.delay_stream_state_bytes, self.hist_bins)
         self.hist = torch.zeros((self.streams, self.hist_bins), dtype=torch.float64,
                                 device=self.device)
         self.angles = None
         self.delays = self.n_peaks = None
         self.reset()
-
-    _flags = StreamingBeamformer._flags
 
     def reset(self, select=None, stream=None):
         """Start the selected streams (flags per stream; None = all) afresh: zero history and
@@ -370,14 +392,7 @@ class StreamingDelayMask:
     def steer(self, angles):
         """New target azimuth per stream in degrees (NaN = the plan's), from the next pushed
         frame; None returns every stream to the plan's."""
-        import torch
-        if angles is None:
-            self.angles = None
-            return
-        a = torch.as_tensor(angles, dtype=torch.float64).to(self.device).contiguous()
-        if tuple(a.shape) != (self.streams,):
-            raise ValueError("angles must have one entry per stream")
-        self.angles = a
+        self.angles = None if angles is None else self._angles(angles)
 
     def push(self, mix, *, active=None, adapt=None, mask=None, stream=None):
         """mix [streams, 2, hops * hop] float32 -> mask [streams, F, hops] float32: column j
@@ -385,9 +400,7 @@ class StreamingDelayMask:
         hops weights."""
         import torch
         from . import engine
-        if mix.dim() != 3 or mix.shape[0] != self.streams:
-            raise ValueError("mix must be float32 [streams, 2, hops * hop] on the device")
-        hops = mix.shape[2] // self.plan.hop
+        hops = self._block(mix).shape[2] // self.plan.hop
         self.delays = torch.full((self.streams, hops, 8), float("nan"), dtype=torch.float64,
                                  device=mix.device)
         self.n_peaks = torch.zeros((self.streams, hops), dtype=torch.int32, device=mix.device)
@@ -432,10 +445,7 @@ class StreamingBlindBeamformer:
 
     def flush(self, **kw):
         """Push one hop of zeros through both: returns the last hop."""
-        import torch
-        z = torch.zeros((self.streams, 2, self.plan.hop), dtype=torch.float32,
-                        device=self.beamformer.device)
-        return self.push(z, **kw)
+        return self.push(self.beamformer._zero_hop(), **kw)
 
 
 def enhance_blind_stream(y_mix, hops_per_push: int = 1, dereverb: bool = False, *,

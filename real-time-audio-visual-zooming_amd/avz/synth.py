@@ -302,25 +302,21 @@ def make_batch_device(batch: int, start: int = 0, n_samples: int = 64000,
     rng="philox": avz_scene_generate — draws and all on the device (make_batch_philox is
                   the host restatement); no host work, so a large shard costs milliseconds.
     """
-    import ctypes as ct
-
     import torch
 
-    from ._lib import check, lib
-    from .engine import _stream_handle
+    from ._args import call, ptr as p
+    from ._lib import lib
     dev = device or torch.device("cuda", torch.cuda.current_device())
     K = n_interferers
     mix = torch.empty((batch, 2, n_samples), dtype=torch.float32, device=dev)
     tgt = torch.empty((batch, n_samples), dtype=torch.float32, device=dev)
     itf = torch.empty((batch, n_samples), dtype=torch.float32, device=dev)
-    p = lambda t: ct.c_void_p(t.data_ptr())  # noqa: E731
     if rng == "philox":
         ws_bytes = lib.avz_scene_generate_workspace_bytes(batch, K, n_samples)
         ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
-        check(lib.avz_scene_generate(batch, start, K, n_samples, seed, d, C_SOUND, float(fs),
-                                     sir_db, snr_db, p(mix), mix.stride(0), mix.stride(1), p(tgt),
-                                     p(itf), tgt.stride(0), p(ws), ws_bytes,
-                                     _stream_handle(None)), "avz_scene_generate")
+        call("avz_scene_generate", batch, start, K, n_samples, seed, d, C_SOUND, float(fs),
+             sir_db, snr_db, p(mix), mix.stride(0), mix.stride(1), p(tgt), p(itf), tgt.stride(0),
+             p(ws), ws_bytes)
         return mix, tgt, itf
     if rng != "host":
         raise ValueError(f"rng must be 'host' or 'philox', not {rng!r}")
@@ -334,10 +330,9 @@ def make_batch_device(batch: int, start: int = 0, n_samples: int = 64000,
     d_noise = torch.from_numpy(noise).to(dev)
     ws_bytes = lib.avz_scene_workspace_bytes(batch, 1 + K, n_samples)
     ws = torch.empty((max(ws_bytes, 4) + 3) // 4, dtype=torch.float32, device=dev)
-    check(lib.avz_scene_mix(batch, 1 + K, n_samples, p(d_src), p(d_ang), p(d_noise), d, C_SOUND,
-                            float(fs), sir_db, snr_db, p(mix), mix.stride(0), mix.stride(1),
-                            p(tgt), p(itf), tgt.stride(0), p(ws), ws_bytes,
-                            _stream_handle(None)), "avz_scene_mix")
+    call("avz_scene_mix", batch, 1 + K, n_samples, p(d_src), p(d_ang), p(d_noise), d, C_SOUND,
+         float(fs), sir_db, snr_db, p(mix), mix.stride(0), mix.stride(1), p(tgt), p(itf),
+         tgt.stride(0), p(ws), ws_bytes)
     return mix, tgt, itf
 
 
@@ -599,8 +594,8 @@ def make_reverb_batch_device(batch: int, start: int = 0, n_samples: int = 64000,
 
     import torch
 
+    from ._args import call, ptr as p
     from ._lib import check, lib
-    from .engine import _stream_handle
     room = room or Room()
     dev = device or torch.device("cuda", torch.cuda.current_device())
     K, n = n_interferers, n_samples
@@ -612,7 +607,6 @@ def make_reverb_batch_device(batch: int, start: int = 0, n_samples: int = 64000,
     itf = torch.empty((batch, n), dtype=torch.float32, device=dev)
     if batch == 0:
         return mix, tgt, itf
-    p = lambda t: ct.c_void_p(t.data_ptr())  # noqa: E731
     ws_fn = (lib.avz_scene_reverb_generate_workspace_bytes if rng == "philox"
              else lib.avz_scene_reverb_workspace_bytes)
     cnt = K if rng == "philox" else 1 + K
@@ -624,25 +618,22 @@ def make_reverb_batch_device(batch: int, start: int = 0, n_samples: int = 64000,
     D3 = ct.c_double * 3
     tp = D3(*(SOURCE_TARGET_POS if target_pos is None else target_pos))
     ip = D3(*(SOURCE_INTERF_POS if interferer_pos is None else interferer_pos))
-    with torch.cuda.device(dev):
-        for b0 in range(0, batch, step):
-            nb = min(step, batch - b0)
-            m, t, i = mix[b0:b0 + nb], tgt[b0:b0 + nb], itf[b0:b0 + nb]
-            if rng == "philox":
-                check(lib.avz_scene_reverb_generate(
-                    ct.byref(r), nb, start + b0, K, n, seed, tp, ip, sir_db, snr_db, p(m),
-                    mix.stride(0), mix.stride(1), p(t), p(i), tgt.stride(0), p(ws), ws_bytes,
-                    _stream_handle(None)), "avz_scene_reverb_generate")
-                continue
-            pos = np.empty((nb, 1 + K, 3))
-            srcs = np.empty((nb, 1 + K, n), np.float32)
-            noise = np.empty((nb, 2, n), np.float32)
-            for b in range(nb):
-                pos[b], srcs[b], noise[b] = reverb_scene_draws(start + b0 + b, n, K, room,
-                                                               target_pos, interferer_pos)
-            d_pos, d_src, d_noise = (torch.from_numpy(a).to(dev) for a in (pos, srcs, noise))
-            check(lib.avz_scene_reverb_mix(
-                ct.byref(r), nb, 1 + K, n, p(d_src), p(d_pos), p(d_noise), sir_db, snr_db, p(m),
-                mix.stride(0), mix.stride(1), p(t), p(i), tgt.stride(0), p(ws), ws_bytes,
-                _stream_handle(None)), "avz_scene_reverb_mix")
+    for b0 in range(0, batch, step):
+        nb = min(step, batch - b0)
+        m, t, i = mix[b0:b0 + nb], tgt[b0:b0 + nb], itf[b0:b0 + nb]
+        if rng == "philox":
+            call("avz_scene_reverb_generate", ct.byref(r), nb, start + b0, K, n, seed, tp, ip,
+                 sir_db, snr_db, p(m), mix.stride(0), mix.stride(1), p(t), p(i), tgt.stride(0),
+                 p(ws), ws_bytes, device=dev)
+            continue
+        pos = np.empty((nb, 1 + K, 3))
+        srcs = np.empty((nb, 1 + K, n), np.float32)
+        noise = np.empty((nb, 2, n), np.float32)
+        for b in range(nb):
+            pos[b], srcs[b], noise[b] = reverb_scene_draws(start + b0 + b, n, K, room,
+                                                           target_pos, interferer_pos)
+        d_pos, d_src, d_noise = (torch.from_numpy(a).to(dev) for a in (pos, srcs, noise))
+        call("avz_scene_reverb_mix", ct.byref(r), nb, 1 + K, n, p(d_src), p(d_pos), p(d_noise),
+             sir_db, snr_db, p(m), mix.stride(0), mix.stride(1), p(t), p(i), tgt.stride(0),
+             p(ws), ws_bytes, device=dev)
     return mix, tgt, itf

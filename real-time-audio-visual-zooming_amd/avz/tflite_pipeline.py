@@ -19,7 +19,6 @@ any device model taking the features.
 """
 from __future__ import annotations
 
-import ctypes as ct
 import os
 import time
 
@@ -27,8 +26,8 @@ import numpy as np
 import torch
 
 from . import wavio
-from ._lib import check, lib
-from .engine import MVDRPlan, _stream_handle, mask_features
+from ._args import call, ptr
+from .engine import MVDRPlan, mask_features
 from .final_pipeline import chunk_table
 
 # tf_lite_version/config.json (read by inference.py:9-25) and inference.py:44-48
@@ -81,7 +80,6 @@ class ChunkedMVDRBeamformer:
         (y [B, S] float32 peak-normalised with + 1e-9, peak [B] before normalisation)."""
         B, _, S = mix.shape
         dev = mix.device
-        st = _stream_handle(stream)
         lengths = [S] * B if lengths is None else [int(x) for x in lengths]
         utt_h, start_h, base_h = chunk_table(lengths, self.hop_c)
         n = len(utt_h)
@@ -90,20 +88,16 @@ class ChunkedMVDRBeamformer:
         base = torch.from_numpy(base_h).to(dev)
         d_len = torch.tensor(lengths, dtype=torch.int32, device=dev)
         items = torch.empty((n, 2, self.chunk), dtype=torch.float32, device=dev)
-        check(lib.avz_chunk_split(n, 2, self.chunk, ct.c_void_p(utt.data_ptr()),
-                                  ct.c_void_p(start.data_ptr()), ct.c_void_p(d_len.data_ptr()),
-                                  ct.c_void_p(mix.data_ptr()), mix.stride(0), mix.stride(1),
-                                  ct.c_void_p(items.data_ptr()), items.stride(0), items.stride(1),
-                                  st), "avz_chunk_split")
+        call("avz_chunk_split", n, 2, self.chunk, ptr(utt), ptr(start), ptr(d_len), ptr(mix),
+             mix.stride(0), mix.stride(1), ptr(items), items.stride(0), items.stride(1),
+             stream=stream)
         mask = mask_fn(self.features(items, stream))
         item_out, _ = self.plan.run(items, ext_mask=mask, stream=stream)
         y = torch.zeros((B, S), dtype=torch.float32, device=dev)
         peak = torch.empty((B,), dtype=torch.float32, device=dev)
-        check(lib.avz_chunk_merge(B, max(lengths), self.hop_c, self.item_out_len,
-                                  ct.c_void_p(d_len.data_ptr()), ct.c_void_p(base.data_ptr()),
-                                  ct.c_void_p(item_out.data_ptr()), item_out.stride(0),
-                                  ct.c_void_p(y.data_ptr()), y.stride(0),
-                                  ct.c_void_p(peak.data_ptr()), 1, 1e-9, st), "avz_chunk_merge")
+        call("avz_chunk_merge", B, max(lengths), self.hop_c, self.item_out_len, ptr(d_len),
+             ptr(base), ptr(item_out), item_out.stride(0), ptr(y), y.stride(0), ptr(peak), 1, 1e-9,
+             stream=stream)
         return y, peak
 
 
