@@ -23,9 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "avz_common.hpp"
 #include "avz_delay_mask.hpp"
-#include "avz_features.hpp"
+#include "avz_frame.hpp"
 
 namespace avz {
 
@@ -43,42 +42,18 @@ constexpr int delay_lds_bytes() {
   return G::LDS_BYTES > G::CARRY_OFF + 4096 ? G::LDS_BYTES : G::CARRY_OFF + 4096;
 }
 
-// Windowed forward transform of this lane group's frame of block (b, f0) into its slot
-// (avz_stft_kernel's: scipy scaling, 2 / N times the periodic Hann).
+// This lane group's frame of the mixture's packed mic pair into its slot (avz_stft_kernel's
+// framing and scaling: frame_transform of avz_frame.hpp).
 template <int N>
-__device__ __forceinline__ void delay_transform(const DelayArgs& A, int b, int f0, int L,
-                                                unsigned char* lds, const cf* twid) {
-  using C = KCfg<N>;
-  constexpr int H = N / 2, PPL = C::PPL;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  typename C::Fft fft;
-  fft.init(lane);
-  LaneMap<N> lm;
-  lm.init(lane);
-  const int my_slot = wave * C::FPW + lm.grp;
-  cf* spec = slot_ptr<N>(lds, my_slot);
-  const float* xb = A.mix + (long long)b * A.mix_stride;
-  const rsrc_t re = make_rsrc(xb, L);
-  const rsrc_t im = make_rsrc(xb + A.ch_stride, L);
-  float wa0, wac, was;
-  {
-    double s, c;
-    sincospi(2.0 * lm.in0 / N, &s, &c);
-    const double sc = 2.0 / N;
-    wa0 = (float)(0.5 * sc);
-    wac = (float)(0.5 * sc * c);
-    was = (float)(0.5 * sc * s);
-  }
-  cf v[PPL];
-  const int s0 = (f0 + my_slot) * H - N / 2 + lm.in0;
-  static_for<0, PPL>([&](auto r) {
-    constexpr int j = (C::IN_STRIDE * 32 / N) * r;
-    constexpr float cr = W32::c[j % 32], sr = -W32::s[j % 32];
-    const float w = fmaf(was, sr, fmaf(-wac, cr, wa0));
-    v[r] = {bload(re, s0 + C::IN_STRIDE * r) * w, bload(im, s0 + C::IN_STRIDE * r) * w};
-  });
-  fft.forward(v, spec, twid);
-  static_for<0, PPL>([&](auto k) { spec[lm.out0 + C::OUT_STRIDE * k] = v[k]; });
+__device__ __forceinline__ void delay_mix_frame(const DelayArgs& A, const FrameBlock<N>& B,
+                                                unsigned char* lds) {
+  Lanes<N> ln;
+  ln.init(lds, threadIdx.x);
+  const float* xb = A.mix + (long long)B.b * A.mix_stride;
+  const rsrc_t re = make_rsrc(xb, B.L), im = make_rsrc(xb + A.ch_stride, B.L);
+  StftWindow<N> win;
+  win.init(ln.lm);
+  frame_transform<N>(ln, re, im, B.s0(ln), win, B.twid);
 }
 
 // Thread -> (bin, frames) of the per-bin phases: bin kk = tid mod N/2 with the Nyquist bin in
@@ -99,20 +74,12 @@ struct BinMap {
 
 template <int N>
 __global__ void __launch_bounds__(kStftThreads, 1) avz_delay_hist_kernel(DelayArgs A) {
-  using C = KCfg<N>;
   using G = Geo<N, kStftThreads>;
-  constexpr int H = G::H;
   extern __shared__ __align__(16) unsigned char lds[];
-  cf* twid = reinterpret_cast<cf*>(lds + G::TW_OFF);
-  C::Fft::fill_twiddles(twid, threadIdx.x, kStftThreads);
-  const int b = blockIdx.x;
-  const int f0 = blockIdx.y * kDelayFrames;
-  const int tid = threadIdx.x;
-  const int L = min(A.len[b], A.max_len);
-  const int T = (L + H - 1) / H + 1;
-  if (f0 >= T || L < N) return;
-  __syncthreads();
-  delay_transform<N>(A, b, f0, L, lds, twid);
+  FrameBlock<N> B;
+  if (!B.init(lds, A.len, A.max_len)) return;
+  const int b = B.b, f0 = B.f0, T = B.T, tid = threadIdx.x;
+  delay_mix_frame<N>(A, B, lds);
   __syncthreads();
 
   // (u, w) of every band pair, in place: Z_f[kk] <- (u, w)
@@ -191,20 +158,12 @@ __global__ void __launch_bounds__(kPeakThreads) avz_delay_peaks_kernel(DelayArgs
 
 template <int N>
 __global__ void __launch_bounds__(kStftThreads, 1) avz_delay_label_kernel(DelayArgs A) {
-  using C = KCfg<N>;
-  using G = Geo<N, kStftThreads>;
-  constexpr int H = G::H, F = G::F;
+  constexpr int F = N / 2 + 1;
   extern __shared__ __align__(16) unsigned char lds[];
-  cf* twid = reinterpret_cast<cf*>(lds + G::TW_OFF);
-  C::Fft::fill_twiddles(twid, threadIdx.x, kStftThreads);
-  const int b = blockIdx.x;
-  const int f0 = blockIdx.y * kDelayFrames;
-  const int tid = threadIdx.x;
-  const int L = min(A.len[b], A.max_len);
-  const int T = (L + H - 1) / H + 1;
-  if (f0 >= T || L < N) return;
-  __syncthreads();
-  delay_transform<N>(A, b, f0, L, lds, twid);
+  FrameBlock<N> B;
+  if (!B.init(lds, A.len, A.max_len)) return;
+  const int b = B.b, f0 = B.f0, T = B.T, tid = threadIdx.x;
+  delay_mix_frame<N>(A, B, lds);
 
   // the bin's rotations e^{i omega_k delta_j}, j = 0 .. J: fp64, rounded to fp32
   BinMap<N> bm;
@@ -245,25 +204,18 @@ __global__ void __launch_bounds__(kStftThreads, 1) avz_delay_label_kernel(DelayA
 
 using namespace avz;
 
-template <int N>
-static int launch_delay_t(const DelayArgs* a, hipStream_t st) {
-  const int lds = delay_lds_bytes<N>();
-  if (!lds_ready<avz_delay_hist_kernel<N>>(lds)) return -3;
-  if (!lds_ready<avz_delay_label_kernel<N>>(lds)) return -3;
-  const dim3 grid(a->batch, a->nblk);
-  hipLaunchKernelGGL(avz_delay_hist_kernel<N>, grid, dim3(kStftThreads), lds, st, *a);
-  if (hipGetLastError() != hipSuccess) return -3;
-  hipLaunchKernelGGL(avz_delay_peaks_kernel, dim3(a->batch), dim3(kPeakThreads), 0, st, *a, N);
-  if (hipGetLastError() != hipSuccess) return -3;
-  hipLaunchKernelGGL(avz_delay_label_kernel<N>, grid, dim3(kStftThreads), lds, st, *a);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 extern "C" int avz_launch_delay_mask(int n_fft, const DelayArgs* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (a->batch <= 0) return 0;
   if (a->p.nb < 1 || a->p.nb > kDelayMaxBins) return -1;
-  if (n_fft == 1024) return launch_delay_t<1024>(a, st);
-  if (n_fft == 512) return launch_delay_t<512>(a, st);
-  return -4;
+  return dispatch_n_fft(n_fft, [&](auto n) {
+    constexpr int N = decltype(n)::value, lds = delay_lds_bytes<N>();
+    const dim3 grid(a->batch, a->nblk);
+    if (!lds_ready<avz_delay_hist_kernel<N>>(lds) || !lds_ready<avz_delay_label_kernel<N>>(lds))
+      return -3;  // both attributes before the first launch
+    int rc = launch<avz_delay_hist_kernel<N>>(grid, kStftThreads, lds, st, *a);
+    if (rc == 0) rc = launch<avz_delay_peaks_kernel>(dim3(a->batch), kPeakThreads, 0, st, *a, N);
+    if (rc == 0) rc = launch<avz_delay_label_kernel<N>>(grid, kStftThreads, lds, st, *a);
+    return rc;
+  });
 }

@@ -28,9 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "avz_common.hpp"
 #include "avz_delay_stream.hpp"
-#include "avz_stream_common.hpp"
+#include "avz_frame.hpp"
 
 namespace avz {
 
@@ -60,7 +59,6 @@ __device__ __forceinline__ int delay_stream_segments(int nb) {
 
 template <int N>
 __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(DelayStreamArgs A) {
-  using C = KCfg<N>;
   using SG = StreamGeo<N>;
   using DG = DelayStreamGeo<N>;
   constexpr int H = SG::H, F = SG::F, NSLOT = SG::NSLOT, L8 = kDelayList;
@@ -76,8 +74,6 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
   const unsigned long long count0 = hdr->count;
 
   extern __shared__ __align__(16) unsigned char lds[];
-  cf* twid = reinterpret_cast<cf*>(lds + SG::TW_OFF);
-  float* win = reinterpret_cast<float*>(lds + SG::WIN_OFF);
   double* h = reinterpret_cast<double*>(lds + DG::H_OFF);
   double* hs0 = reinterpret_cast<double*>(lds + DG::HS_OFF);
   double* c_h = reinterpret_cast<double*>(lds + DG::CH_OFF);
@@ -85,7 +81,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
   double* seg = reinterpret_cast<double*>(lds + DG::SEG_OFF);
   double* tab = reinterpret_cast<double*>(lds + DG::LIST_OFF);  // [8][8]
   int* Jt = reinterpret_cast<int*>(lds + DG::J_OFF);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
 
   const bool adapt = !A.adapt || A.adapt[s] != 0;
   const double lam = A.forget;
@@ -93,17 +89,11 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
   if (theta != theta) theta = A.p.plan_angle;  // NaN: the plan's
   const double d_t = delay_target(A.p, theta);
 
-  C::Fft::fill_twiddles(twid, tid, kStreamThreads);
-  for (int n = tid; n < N; n += kStreamThreads) win[n] = A.xwin[n];
+  StreamBlock<N> sb;
+  sb.stage(lds, A.xwin, tid);
   for (int i = tid; i < nb; i += kStreamThreads) h[i] = h_g[i];
   __syncthreads();
-
-  typename C::Fft fft;
-  fft.init(lane);
-  LaneMap<N> lm;
-  lm.init(lane);
-  const int my_slot = wave * C::FPW + lm.grp;
-  cf* spec = slot_ptr<N>(lds, my_slot);
+  sb.init(lds);
 
   const float* x0 = A.mix + (long long)s * A.mix_stride;
   const float* x1 = x0 + A.ch_stride;
@@ -114,9 +104,9 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
 
   for (int j0 = 0; j0 < A.hops; j0 += NSLOT) {
     const int nf = min(NSLOT, A.hops - j0);
-    const bool valid = my_slot < nf;
+    const bool valid = sb.my_slot < nf;
 
-    stream_transform<N>(fft, lm, x0, x1, prev, prev + H, j0 + my_slot, valid, win, spec, twid);
+    stream_transform<N>(sb, x0, x1, prev, prev + H, j0 + sb.my_slot, valid);
     __syncthreads();
 
     // (u, w) of every band pair, in place: Z_f[k] <- (u, w)
@@ -167,7 +157,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
     }
 
     // the spectra again: the pairs overwrote the band's bins
-    stream_transform<N>(fft, lm, x0, x1, prev, prev + H, j0 + my_slot, valid, win, spec, twid);
+    stream_transform<N>(sb, x0, x1, prev, prev + H, j0 + sb.my_slot, valid);
     __syncthreads();
 
     // labels: bin kk = k with the Nyquist bin in place of DC (omega = 0: every cost ties)
@@ -207,11 +197,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_delay_stream_kernel(Del
   }
 
   // the state after the call's last frame
-  const long long qlast = (long long)(A.hops - 1) * H;
-  for (int m = tid; m < H; m += kStreamThreads) {
-    prev[m] = x0[qlast + m];
-    prev[H + m] = x1[qlast + m];
-  }
+  save_last_hop<H>(prev, x0, x1, A.hops, tid);
   for (int i = tid; i < nb; i += kStreamThreads) {
     h_g[i] = h[i];
     if (A.hist_out) A.hist_out[(long long)s * nb + i] = h[i];
@@ -225,9 +211,8 @@ __global__ void __launch_bounds__(kStreamThreads) avz_delay_stream_reset_kernel(
   const int s = blockIdx.x;
   if (A.select && A.select[s] == 0) return;
   unsigned char* st = A.state + (long long)s * A.state_stride;
-  uint32_t* words = reinterpret_cast<uint32_t*>(st);
-  const int n_words = (int)(A.state_stride / 4);
-  for (int i = 4 + threadIdx.x; i < n_words; i += kStreamThreads) words[i] = 0u;
+  static_assert(sizeof(DelayStreamHeader) % 4 == 0, "zero_state works in words");
+  zero_state(st, sizeof(DelayStreamHeader), A.state_stride);
   if (threadIdx.x == 0) {
     DelayStreamHeader* hdr = reinterpret_cast<DelayStreamHeader*>(st);
     hdr->count = 0ull;
@@ -240,28 +225,18 @@ __global__ void __launch_bounds__(kStreamThreads) avz_delay_stream_reset_kernel(
 
 using namespace avz;
 
-static_assert(sizeof(DelayStreamHeader) == 16, "the reset kernel zeroes from word 4");
-
-template <int N>
-static int launch_delay_stream_t(const DelayStreamArgs* a, hipStream_t st) {
-  const int lds = DelayStreamGeo<N>::LDS_BYTES;
-  if (!lds_ready<avz_delay_stream_kernel<N>>(lds)) return -3;
-  hipLaunchKernelGGL(avz_delay_stream_kernel<N>, dim3(a->streams), dim3(kStreamThreads), lds, st,
-                     *a);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 extern "C" int avz_launch_delay_stream_push(int n_fft, const DelayStreamArgs* a, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (a->p.nb < 1 || a->p.nb > kDelayMaxBins) return -1;
-  if (n_fft == 1024) return launch_delay_stream_t<1024>(a, st);
-  if (n_fft == 512) return launch_delay_stream_t<512>(a, st);
-  return -4;
+  return dispatch_n_fft(n_fft, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    return launch<avz_delay_stream_kernel<N>>(dim3(a->streams), kStreamThreads,
+                                              DelayStreamGeo<N>::LDS_BYTES, (hipStream_t)stream,
+                                              *a);
+  });
 }
 
 extern "C" int avz_launch_delay_stream_reset(int n_fft, const DelayStreamArgs* a, void* stream) {
   if (n_fft != 1024 && n_fft != 512) return -4;
-  hipLaunchKernelGGL(avz_delay_stream_reset_kernel, dim3(a->streams), dim3(kStreamThreads), 0,
-                     (hipStream_t)stream, *a, n_fft);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch<avz_delay_stream_reset_kernel>(dim3(a->streams), kStreamThreads, 0,
+                                               (hipStream_t)stream, *a, n_fft);
 }

@@ -24,8 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "avz_common.hpp"
-#include "avz_stream_common.hpp"
+#include "avz_frame.hpp"
 
 namespace avz {
 
@@ -37,11 +36,9 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArg
   const int s = blockIdx.x;
   if (S.active && S.active[s] == 0) return;
   extern __shared__ __align__(16) unsigned char lds[];
-  cf* twid = reinterpret_cast<cf*>(lds + SG::TW_OFF);
-  float* win = reinterpret_cast<float*>(lds + SG::WIN_OFF);
   float* tail = reinterpret_cast<float*>(lds + SG::TAIL_OFF);
   uint32_t* nbits = reinterpret_cast<uint32_t*>(lds + SG::BITS_OFF);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
 
   const StreamLayout lay(N);
   unsigned char* st = S.state + (long long)s * S.state_stride;
@@ -54,17 +51,11 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArg
   const bool adapt = !S.adapt || S.adapt[s] != 0;
   const double lam = S.forget;
 
-  C::Fft::fill_twiddles(twid, tid, kStreamThreads);
-  for (int n = tid; n < N; n += kStreamThreads) win[n] = P.xwin[n];
+  StreamBlock<N> sb;
+  sb.stage(lds, P.xwin, tid);
   for (int m = tid; m < H; m += kStreamThreads) tail[m] = tail_g[m];
   __syncthreads();
-
-  typename C::Fft fft;
-  fft.init(lane);
-  LaneMap<N> lm;
-  lm.init(lane);
-  const int my_slot = wave * C::FPW + lm.grp;
-  cf* spec = slot_ptr<N>(lds, my_slot);
+  sb.init(lds);
 
   const float* x0 = S.mix + (long long)s * S.mix_stride;
   const float* x1 = x0 + S.ch_stride;
@@ -74,13 +65,12 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArg
 
   for (int j0 = 0; j0 < S.hops; j0 += NSLOT) {
     const int nf = min(NSLOT, S.hops - j0);
-    const bool valid = my_slot < nf;
+    const bool valid = sb.my_slot < nf;
     const bool last = j0 + nf == S.hops;
 
     if constexpr (MASK == MASK_IBM) {
       // reference pair -> noise bits: bit f of nbits[k] = frame j0 + f of bin k is noise
-      stream_transform<N>(fft, lm, rt, ri, prev + 2 * H, prev + 3 * H, j0 + my_slot, valid, win,
-                          spec, twid);
+      stream_transform<N>(sb, rt, ri, prev + 2 * H, prev + 3 * H, j0 + sb.my_slot, valid);
       __syncthreads();
       for (int k = tid; k < F; k += kStreamThreads) {
         uint32_t bits = 0;
@@ -95,7 +85,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArg
       __syncthreads();  // every slot has been read before its lane group overwrites it
     }
 
-    stream_transform<N>(fft, lm, x0, x1, prev, prev + H, j0 + my_slot, valid, win, spec, twid);
+    stream_transform<N>(sb, x0, x1, prev, prev + H, j0 + sb.my_slot, valid);
     __syncthreads();
 
     // per bin: recursion, solve and apply over the group's frames, in order
@@ -169,13 +159,13 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArg
     {
       cf v[C::PPL];
       static_for<0, C::PPL>(
-          [&](auto r) { v[r] = c_conj(spec[lm.in0 + C::IN_STRIDE * r]); });
+          [&](auto r) { v[r] = c_conj(sb.spec[sb.lm.in0 + C::IN_STRIDE * r]); });
       __builtin_amdgcn_wave_barrier();  // the group's reads precede the transform's stores
-      fft.forward(v, spec, twid);
-      float* gf = reinterpret_cast<float*>(spec);
+      sb.fft.forward(v, sb.spec, sb.twid);
+      float* gf = reinterpret_cast<float*>(sb.spec);
       static_for<0, C::PPL>([&](auto k) {
-        const int n = lm.out0 + C::OUT_STRIDE * k;
-        gf[n] = (0.5f * v[k].x) * win[n];
+        const int n = sb.lm.out0 + C::OUT_STRIDE * k;
+        gf[n] = (0.5f * v[k].x) * sb.win[n];
       });
     }
     __syncthreads();
@@ -190,11 +180,8 @@ __global__ void __launch_bounds__(kStreamThreads, 1) avz_stream_kernel(StreamArg
       const bool first = count0 + (unsigned long long)(j0 + f) == 0ull;
       float o[4];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float w0 = win[m + i], w1 = win[m + i + H];
-        const float den = fmaf(w1, w1, w0 * w0);
-        o[i] = first ? 0.0f : (gp[i] + gc[i]) / den;
-      }
+      for (int i = 0; i < 4; ++i)
+        o[i] = first ? 0.0f : (gp[i] + gc[i]) / ola_den<H>(sb.win, m + i);
       *reinterpret_cast<float4*>(orow + (long long)(j0 + f) * H + m) =
           make_float4(o[0], o[1], o[2], o[3]);
     }
@@ -225,9 +212,7 @@ __global__ void __launch_bounds__(kStreamThreads) avz_stream_reset_kernel(Stream
   if (S.select && S.select[s] == 0) return;
   const StreamLayout lay(n_fft);
   unsigned char* st = S.state + (long long)s * S.state_stride;
-  uint32_t* words = reinterpret_cast<uint32_t*>(st);
-  const int n_zero = (int)(lay.steer_off / 4);
-  for (int i = threadIdx.x; i < n_zero; i += kStreamThreads) words[i] = 0u;
+  zero_state(st, 0, lay.steer_off);
   double* d = reinterpret_cast<double*>(st + lay.steer_off);
   const int n_steer = (n_fft / 2 + 1) * 4;
   for (int i = threadIdx.x; i < n_steer; i += kStreamThreads) d[i] = steer[i];
@@ -263,44 +248,32 @@ __global__ void __launch_bounds__(kStreamThreads) avz_stream_steer_kernel(Stream
 
 using namespace avz;
 
-template <int N, int MASK>
-static int launch_stream_t(const StreamArgs* s, const ChainArgs* p, hipStream_t st) {
-  auto kern = avz_stream_kernel<N, MASK>;
-  const int lds = StreamGeo<N>::LDS_BYTES;
-  if (!lds_ready<avz_stream_kernel<N, MASK>>(lds)) return -3;
-  hipLaunchKernelGGL(kern, dim3(s->streams), dim3(kStreamThreads), lds, st, *s, *p);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-template <int N>
-static int launch_stream_n(int mask_mode, const StreamArgs* s, const ChainArgs* p,
-                           hipStream_t st) {
-  switch (mask_mode) {
-    case MASK_IBM: return launch_stream_t<N, MASK_IBM>(s, p, st);
-    case MASK_EXTERNAL: return launch_stream_t<N, MASK_EXTERNAL>(s, p, st);
-    case MASK_ONES: return launch_stream_t<N, MASK_ONES>(s, p, st);
-  }
-  return -4;
-}
-
 extern "C" int avz_launch_stream_push(int n_fft, int mask_mode, const StreamArgs* s,
                                       const ChainArgs* p, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (n_fft == 1024) return launch_stream_n<1024>(mask_mode, s, p, st);
-  if (n_fft == 512) return launch_stream_n<512>(mask_mode, s, p, st);
-  return -4;
+  return dispatch_n_fft(n_fft, [&](auto n) {
+    constexpr int N = decltype(n)::value, lds = StreamGeo<N>::LDS_BYTES;
+    const dim3 grid(s->streams);
+    hipStream_t st = (hipStream_t)stream;
+    switch (mask_mode) {
+      case MASK_IBM:
+        return launch<avz_stream_kernel<N, MASK_IBM>>(grid, kStreamThreads, lds, st, *s, *p);
+      case MASK_EXTERNAL:
+        return launch<avz_stream_kernel<N, MASK_EXTERNAL>>(grid, kStreamThreads, lds, st, *s, *p);
+      case MASK_ONES:
+        return launch<avz_stream_kernel<N, MASK_ONES>>(grid, kStreamThreads, lds, st, *s, *p);
+    }
+    return -4;
+  });
 }
 
 extern "C" int avz_launch_stream_reset(int n_fft, const StreamArgs* s, const double* plan_steer,
                                        void* stream) {
-  hipLaunchKernelGGL(avz_stream_reset_kernel, dim3(s->streams), dim3(kStreamThreads), 0,
-                     (hipStream_t)stream, *s, n_fft, plan_steer);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch<avz_stream_reset_kernel>(dim3(s->streams), kStreamThreads, 0, (hipStream_t)stream,
+                                         *s, n_fft, plan_steer);
 }
 
 extern "C" int avz_launch_stream_steer(int n_fft, const StreamArgs* s, double mic_d,
                                        double c_sound, double fs, void* stream) {
-  hipLaunchKernelGGL(avz_stream_steer_kernel, dim3(s->streams), dim3(kStreamThreads), 0,
-                     (hipStream_t)stream, *s, n_fft, mic_d, c_sound, fs);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch<avz_stream_steer_kernel>(dim3(s->streams), kStreamThreads, 0, (hipStream_t)stream,
+                                         *s, n_fft, mic_d, c_sound, fs);
 }

@@ -20,69 +20,30 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "avz_common.hpp"
-#include "avz_features.hpp"
+#include "avz_frame.hpp"
 
 namespace avz {
 
-// Windowed forward transform of the frame at sample s0 (lane part included) of the packed
-// pair re + i im into the lane group's slot, scipy scaling (2 / N times the periodic Hann).
-template <int N>
-__device__ __forceinline__ void train_transform(typename KCfg<N>::Fft& fft, const LaneMap<N>& lm,
-                                                rsrc_t re, rsrc_t im, int s0, float wa0,
-                                                float wac, float was, cf* spec, const cf* twid) {
-  using C = KCfg<N>;
-  constexpr int PPL = C::PPL;
-  cf v[PPL];
-  static_for<0, PPL>([&](auto r) {
-    constexpr int j = (C::IN_STRIDE * 32 / N) * r;
-    constexpr float cr = W32::c[j % 32], sr = -W32::s[j % 32];
-    const float w = fmaf(was, sr, fmaf(-wac, cr, wa0));
-    v[r] = {bload(re, s0 + C::IN_STRIDE * r) * w, bload(im, s0 + C::IN_STRIDE * r) * w};
-  });
-  fft.forward(v, spec, twid);
-  static_for<0, PPL>([&](auto k) { spec[lm.out0 + C::OUT_STRIDE * k] = v[k]; });
-}
-
 template <int N, int FEAT>
 __global__ void __launch_bounds__(kStftThreads, 1) avz_train_kernel(TrainArgs T_) {
-  using C = KCfg<N>;
   using G = Geo<N, kStftThreads>;
-  constexpr int H = G::H, F = G::F, NSLOT = G::NSLOT;
+  constexpr int F = G::F, NSLOT = G::NSLOT;
   const StftArgs& A = T_.s;
   extern __shared__ __align__(16) unsigned char lds[];
-  cf* twid = reinterpret_cast<cf*>(lds + G::TW_OFF);
-  C::Fft::fill_twiddles(twid, threadIdx.x, kStftThreads);
-  const int b = blockIdx.x;
-  const int f0 = blockIdx.y * NSLOT;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int L = min(A.len[b], A.max_len);
-  const int T = (L + H - 1) / H + 1;
-  if (f0 >= T || L < N) return;
-  __syncthreads();
+  FrameBlock<N> B;
+  if (!B.init(lds, A.len, A.max_len)) return;
+  const int b = B.b, f0 = B.f0, L = B.L, T = B.T, tid = threadIdx.x;
 
-  typename C::Fft fft;
-  fft.init(lane);
-  LaneMap<N> lm;
-  lm.init(lane);
-  const int my_slot = wave * C::FPW + lm.grp;
-  cf* spec = slot_ptr<N>(lds, my_slot);
-  float wa0, wac, was;
-  {
-    double s, c;
-    sincospi(2.0 * lm.in0 / N, &s, &c);
-    const double sc = 2.0 / N;
-    wa0 = (float)(0.5 * sc);
-    wac = (float)(0.5 * sc * c);
-    was = (float)(0.5 * sc * s);
-  }
-  const int s0 = (f0 + my_slot) * H - N / 2 + lm.in0;
+  Lanes<N> ln;
+  ln.init(lds, tid);
+  StftWindow<N> win;
+  win.init(ln.lm);
+  const int s0 = B.s0(ln);
 
   // pass 1: the mic pair -> features
   {
     const float* xb = A.x + (long long)b * A.x_stride;
-    train_transform<N>(fft, lm, make_rsrc(xb, L), make_rsrc(xb + A.ch_stride, L), s0, wa0, wac,
-                       was, spec, twid);
+    frame_transform<N>(ln, make_rsrc(xb, L), make_rsrc(xb + A.ch_stride, L), s0, win, B.twid);
   }
   __syncthreads();
   for (int idx = tid; idx < F * NSLOT; idx += kStftThreads) {
@@ -97,9 +58,8 @@ __global__ void __launch_bounds__(kStftThreads, 1) avz_train_kernel(TrainArgs T_
   __syncthreads();  // every slot has been read before its lane group overwrites it
 
   // pass 2: the reference pair -> label
-  train_transform<N>(fft, lm, make_rsrc(T_.tgt + (long long)b * T_.ref_stride, L),
-                     make_rsrc(T_.itf + (long long)b * T_.ref_stride, L), s0, wa0, wac, was, spec,
-                     twid);
+  frame_transform<N>(ln, make_rsrc(T_.tgt + (long long)b * T_.ref_stride, L),
+                     make_rsrc(T_.itf + (long long)b * T_.ref_stride, L), s0, win, B.twid);
   __syncthreads();
   float* lab = T_.label + (long long)b * T_.l_sb;
   for (int idx = tid; idx < F * NSLOT; idx += kStftThreads) {
@@ -118,29 +78,14 @@ __global__ void __launch_bounds__(kStftThreads, 1) avz_train_kernel(TrainArgs T_
 
 using namespace avz;
 
-template <int N, int FEAT>
-static int launch_train_t(const TrainArgs* a, hipStream_t st) {
-  auto kern = avz_train_kernel<N, FEAT>;
-  const int lds = Geo<N, kStftThreads>::LDS_BYTES;
-  if (!lds_ready<avz_train_kernel<N, FEAT>>(lds)) return -3;
-  constexpr int NS = Geo<N, kStftThreads>::NSLOT;
-  dim3 grid(a->s.batch, (a->s.max_frames + NS - 1) / NS);
-  hipLaunchKernelGGL(kern, grid, dim3(kStftThreads), lds, st, *a);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 extern "C" int avz_launch_train(int n_fft, const TrainArgs* a, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   if (a->s.batch <= 0) return 0;
-  switch (a->s.feat) {
-    case FEAT_LOGMAG_IPD:
-      if (n_fft == 1024) return launch_train_t<1024, FEAT_LOGMAG_IPD>(a, st);
-      if (n_fft == 512) return launch_train_t<512, FEAT_LOGMAG_IPD>(a, st);
-      break;
-    case FEAT_TFLITE:
-      if (n_fft == 1024) return launch_train_t<1024, FEAT_TFLITE>(a, st);
-      if (n_fft == 512) return launch_train_t<512, FEAT_TFLITE>(a, st);
-      break;
-  }
-  return -4;
+  return dispatch_feat<false>(a->s.feat, [&](auto feat) {
+    return dispatch_n_fft(n_fft, [&](auto n) {
+      constexpr int N = decltype(n)::value, FEAT = decltype(feat)::value;
+      return launch<avz_train_kernel<N, FEAT>>(FrameBlock<N>::grid(a->s.batch, a->s.max_frames),
+                                               kStftThreads, FrameBlock<N>::G::LDS_BYTES,
+                                               (hipStream_t)stream, *a);
+    });
+  });
 }

@@ -25,8 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "avz_common.hpp"
-#include "avz_stream_common.hpp"
+#include "avz_frame.hpp"
 
 namespace avz {
 
@@ -37,10 +36,8 @@ template <int N>
 struct WpeStreamGeo {
   using SG = StreamGeo<N>;
   static constexpr int H = N / 2, F = N / 2 + 1;
-  // LDS map: [FFT slots][twiddles][window N f32][tails 2 x H f32]
-  static constexpr int TW_OFF = SG::TW_OFF;
-  static constexpr int WIN_OFF = SG::WIN_OFF;
-  static constexpr int TAIL_OFF = WIN_OFF + N * 4;
+  // LDS map: StreamGeo<N>'s [FFT slots][twiddles][window N f32], then [tails 2 x H f32]
+  static constexpr int TAIL_OFF = SG::TAIL_OFF;
   static constexpr int LDS_BYTES = TAIL_OFF + 2 * H * 4;
   static_assert(KCfg<N>::GROUP_BYTES >= N * 8, "a slot holds both mics' frame");
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
@@ -91,36 +88,27 @@ __device__ __forceinline__ double group_sum(double v) {
 template <int N>
 __global__ void __launch_bounds__(kStreamThreads, 1)
     avz_wpe_stream_analysis_kernel(WpeStreamArgs S, const float* xwin) {
-  using C = KCfg<N>;
   using WG = WpeStreamGeo<N>;
   constexpr int H = WG::H, F = WG::F;
   const int s = blockIdx.x;
   unsigned char* st = wpe_stream_block(S, s, N);
   if (!st) return;
   extern __shared__ __align__(16) unsigned char lds[];
-  cf* twid = reinterpret_cast<cf*>(lds + WG::TW_OFF);
-  float* win = reinterpret_cast<float*>(lds + WG::WIN_OFF);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
 
   const WpeStreamLayout lay(N, S.taps, S.delay);
   const unsigned long long count0 = reinterpret_cast<const WpeHeader*>(st)->count;
   float* prev = reinterpret_cast<float*>(st + lay.prev_off);  // [2][H]
   float4* ring = reinterpret_cast<float4*>(st + lay.ring_off);
 
-  C::Fft::fill_twiddles(twid, tid, kStreamThreads);
-  for (int n = tid; n < N; n += kStreamThreads) win[n] = xwin[n];
+  StreamBlock<N> sb;
+  sb.stage(lds, xwin, tid);
   __syncthreads();
-
-  typename C::Fft fft;
-  fft.init(lane);
-  LaneMap<N> lm;
-  lm.init(lane);
-  const int my_slot = wave * C::FPW + lm.grp;
-  cf* spec = slot_ptr<N>(lds, my_slot);
+  sb.init(lds);
 
   const float* x0 = S.mix + (long long)s * S.mix_stride + (long long)S.j0 * H;
   const float* x1 = x0 + S.ch_stride;
-  stream_transform<N>(fft, lm, x0, x1, prev, prev + H, my_slot, my_slot < S.nf, win, spec, twid);
+  stream_transform<N>(sb, x0, x1, prev, prev + H, sb.my_slot, sb.my_slot < S.nf);
   __syncthreads();
 
   for (int k = tid; k < F; k += kStreamThreads) {
@@ -139,11 +127,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1)
     }
   }
   // the round's last hop is the next round's previous one (the transforms have read prev)
-  const long long qlast = (long long)(S.nf - 1) * H;
-  for (int m = tid; m < H; m += kStreamThreads) {
-    prev[m] = x0[qlast + m];
-    prev[H + m] = x1[qlast + m];
-  }
+  save_last_hop<H>(prev, x0, x1, S.nf, tid);
 }
 
 // --------------------------------------------------------------------------------------- rls
@@ -318,10 +302,8 @@ __global__ void __launch_bounds__(kStreamThreads, 1)
   unsigned char* st = wpe_stream_block(S, s, N);
   if (!st) return;
   extern __shared__ __align__(16) unsigned char lds[];
-  cf* twid = reinterpret_cast<cf*>(lds + WG::TW_OFF);
-  float* win = reinterpret_cast<float*>(lds + WG::WIN_OFF);
   float* tail = reinterpret_cast<float*>(lds + WG::TAIL_OFF);  // [2][H]
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x;
 
   const WpeStreamLayout lay(N, S.taps, S.delay);
   WpeHeader* hdr = reinterpret_cast<WpeHeader*>(st);
@@ -329,27 +311,21 @@ __global__ void __launch_bounds__(kStreamThreads, 1)
   float* tail_g = reinterpret_cast<float*>(st + lay.tail_off);
   const float4* zr = reinterpret_cast<const float4*>(st + lay.zr_off);
 
-  C::Fft::fill_twiddles(twid, tid, kStreamThreads);
-  for (int n = tid; n < N; n += kStreamThreads) win[n] = xwin[n];
+  StreamBlock<N> sb;
+  sb.stage(lds, xwin, tid);
   for (int m = tid; m < 2 * H; m += kStreamThreads) tail[m] = tail_g[m];
   __syncthreads();
-
-  typename C::Fft fft;
-  fft.init(lane);
-  LaneMap<N> lm;
-  lm.init(lane);
-  const int my_slot = wave * C::FPW + lm.grp;
-  cf* spec = slot_ptr<N>(lds, my_slot);
+  sb.init(lds);
 
   // P = Z0 + i Z1 extended Hermitian-wise per mic: ifft(P) = g0 + i g1 with both real. The
   // inverse is conj FFT conj: FFT(conj P)[n] = N (g0[n] - i g1[n]); times sum(w) w[n] / N.
   {
-    const bool valid = my_slot < S.nf;
-    const unsigned long long t = count0 + (unsigned long long)my_slot;
+    const bool valid = sb.my_slot < S.nf;
+    const unsigned long long t = count0 + (unsigned long long)sb.my_slot;
     const float4* zt = zr + (long long)(t % kWpeStreamRound) * F;
     cf v[C::PPL];
     static_for<0, C::PPL>([&](auto r) {
-      const int n = lm.in0 + C::IN_STRIDE * r;
+      const int n = sb.lm.in0 + C::IN_STRIDE * r;
       const int k = n <= H ? n : N - n;
       float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
       if (valid) z = zt[k];
@@ -358,10 +334,10 @@ __global__ void __launch_bounds__(kStreamThreads, 1)
       v[r] = c_conj(P);
     });
     __builtin_amdgcn_wave_barrier();
-    fft.forward(v, spec, twid);
+    sb.fft.forward(v, sb.spec, sb.twid);
     static_for<0, C::PPL>([&](auto q) {
-      const int n = lm.out0 + C::OUT_STRIDE * q;
-      spec[n] = cf{(0.5f * v[q].x) * win[n], (-0.5f * v[q].y) * win[n]};
+      const int n = sb.lm.out0 + C::OUT_STRIDE * q;
+      sb.spec[n] = cf{(0.5f * v[q].x) * sb.win[n], (-0.5f * v[q].y) * sb.win[n]};
     });
   }
   __syncthreads();
@@ -384,9 +360,7 @@ __global__ void __launch_bounds__(kStreamThreads, 1)
         const cf g = slot_ptr<N>(lds, f - 1)[H + q + i];
         pre = m ? g.y : g.x;
       }
-      const float w0 = win[q + i], w1 = win[q + i + H];
-      const float den = fmaf(w1, w1, w0 * w0);
-      o[i] = first ? 0.0f : (pre + cur) / den;
+      o[i] = first ? 0.0f : (pre + cur) / ola_den<H>(sb.win, q + i);
     }
     float* orow = S.out + (long long)s * S.out_stride + (long long)m * S.out_ch_stride;
     *reinterpret_cast<float4*>(orow + (long long)(S.j0 + f) * H + q) =
@@ -407,9 +381,7 @@ __global__ void __launch_bounds__(kStreamThreads)
   if (S.select && S.select[s] == 0) return;
   const WpeStreamLayout lay(n_fft, S.taps, S.delay);
   unsigned char* st = S.state + (long long)s * S.state_stride;
-  uint32_t* words = reinterpret_cast<uint32_t*>(st);
-  const long long n_zero = lay.q_off / 4;
-  for (long long i = threadIdx.x; i < n_zero; i += kStreamThreads) words[i] = 0u;
+  zero_state(st, 0, lay.q_off);
   double2* Q = reinterpret_cast<double2*>(st + lay.q_off);
   const long long n_q = (long long)(n_fft / 2 + 1) * lay.tri;
   for (long long e = threadIdx.x; e < n_q; e += kStreamThreads) {
@@ -459,14 +431,12 @@ static int launch_wpe_stream_n(const WpeStreamArgs* a, const float* xwin, hipStr
 extern "C" int avz_launch_wpe_stream_push(int n_fft, const WpeStreamArgs* a, const float* xwin,
                                           void* stream) {
   static_assert(kWpeGroups * wpe_group_lds(32) <= 160 * 1024, "LDS budget at n = 32");
-  hipStream_t st = (hipStream_t)stream;
-  if (n_fft == 1024) return launch_wpe_stream_n<1024>(a, xwin, st);
-  if (n_fft == 512) return launch_wpe_stream_n<512>(a, xwin, st);
-  return -4;
+  return dispatch_n_fft(n_fft, [&](auto n) {
+    return launch_wpe_stream_n<decltype(n)::value>(a, xwin, (hipStream_t)stream);
+  });
 }
 
 extern "C" int avz_launch_wpe_stream_reset(int n_fft, const WpeStreamArgs* a, void* stream) {
-  hipLaunchKernelGGL(avz_wpe_stream_reset_kernel, dim3(a->streams), dim3(kStreamThreads), 0,
-                     (hipStream_t)stream, *a, n_fft);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  return launch<avz_wpe_stream_reset_kernel>(dim3(a->streams), kStreamThreads, 0,
+                                             (hipStream_t)stream, *a, n_fft);
 }
